@@ -150,6 +150,32 @@ def cpu_baseline(example: str, N: int, H: int, budget_s: float = 16.0, min_wall_
                       f"a CPU restatement, not the JAX reference (not installable) -- a reported baseline, no quality claim"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """`arrays` as out_dir/<name>.npy, float32 (float64 kept).  An array that would take the total past DUMP_MAX_BYTES is cut to a fixed,
+    seeded sample of its rows (sorted; their indices in <name>_rows.npy)."""
+    if not os.path.isdir(out_dir):              # a directory made here ignores itself (a dump inside the checkout leaves `git status` clean)
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:
+            f.write("*\n")
+    names = sorted(arrays, key=lambda k: arrays[k].nbytes)          # smallest first: each takes an equal share of what is left
+    budget = DUMP_MAX_BYTES - 2 * 128 * len(names)                  # (room for the .npy headers)
+    for i, name in enumerate(names):
+        a = np.asarray(arrays[name])
+        a = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+        share = budget // (len(names) - i)
+        if a.nbytes > share:
+            row_bytes = a.nbytes // a.shape[0] + 8                  # a row and its float64 index
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, share // row_bytes), replace=False)).astype(np.float64)
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows)
+            budget -= rows.nbytes
+            a = a[rows.astype(np.int64)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        budget -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -171,6 +197,9 @@ def main():
                          "every iteration), so that per-dispatch averages of rocprofv3 are those of the headline launch")
     ap.add_argument("--option", action="append", default=[], metavar="KEY=INT",
                     help="a field of dial_options (include/dial_mpc.h), e.g. --option no_relay=1; the library reads no environment variables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed reverse_once returned (Ybar, rews, qbar, qdbar, xbar, "
+                         "new_noise_scale) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
 
     # stdout carries exactly ONE line, the JSON record: whatever libraries print while the run is in progress (RCCL
@@ -246,34 +275,38 @@ def main():
         if args.host_noise else [None] * 4
     sigma = mbdpi.sigma_control.clone()
 
-    def timed_iterations(pl, sts, steps, warmup, host_eps=None, pattern=(True,)):
+    def timed_iterations(pl, sts, steps, warmup, host_eps=None, pattern=(True,), last=None):
         """`warmup` untimed + exactly `steps` timed reverse_once calls of planner `pl`, bracketed by a barrier and a device
         synchronize on both sides; returns (max over ranks of the elapsed seconds, kernel ms total, launches).
         pattern: the want_bars flag of call i is pattern[i % len(pattern)] -- (True,) = the FULL iteration (every output of
         the reference's reverse_once: the headline), (False,) = the lean iteration (mean action only, what a plan asks of
-        every annealing iteration but its last), (False, ..., True) = a plan's own sequence."""
+        every annealing iteration but its last), (False, ..., True) = a plan's own sequence.
+        last: a dict that receives, as host arrays after the timed region, what the last timed call returned (Ybar + its info)."""
         Yl = torch.zeros((pl.args.Hnode + 1, pl.nu), dtype=torch.float32, device=dev)
 
         def one_step(i, Yl):
             eps = host_eps[i % len(host_eps)] if host_eps is not None else None   # None: Philox noise inside the rollout kernel
-            _, Yl, _ = pl.reverse_once(sts[i % len(sts)], None, Yl, pl.sigma_control, eps=eps, want_bars=pattern[i % len(pattern)])
-            return Yl
+            _, Yl, info = pl.reverse_once(sts[i % len(sts)], None, Yl, pl.sigma_control, eps=eps, want_bars=pattern[i % len(pattern)])
+            return Yl, info
 
         for i in range(warmup):
-            Yl = one_step(i, Yl)
+            Yl, _ = one_step(i, Yl)
         pl.ctx.set_timing(True)
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        info = None
         for i in range(steps):
-            Yl = one_step(i, Yl)
+            Yl, info = one_step(i, Yl)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         t1 = time.perf_counter()
         k_ms, n_launch = pl.ctx.rollout_ms()
         pl.ctx.set_timing(False)
+        if last is not None and info is not None:   # (each call returns tensors of its own: nothing later overwrites them)
+            last.update({k: v.cpu().numpy() for k, v in dict(info, Ybar=Yl).items() if v is not None})
         el = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
         if world > 1:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -319,8 +352,11 @@ def main():
             lat.append((time.perf_counter() - a) * 1e3)
 
     # ---- the headline: W untimed + exactly K timed FULL iterations
+    last = {}
     elapsed, kernel_ms, launches = timed_iterations(mbdpi, states, args.steps, args.warmup,
-                                                    eps_pool if args.host_noise else None)
+                                                    eps_pool if args.host_noise else None, last=last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     iteration_modes = {
         "ms_per_step_full": elapsed / args.steps * 1e3, "ms_per_step_lean": el_lean / lean_steps * 1e3,
         "ms_per_step_plan_pattern": el_plan / lean_steps * 1e3, "plan_pattern": f"{dial_config.Ndiffuse - 1} lean + 1 full",

@@ -7,7 +7,7 @@ import pytest
 from dial_mpc_amd import mjcf
 from dial_mpc_amd.envs.base_env import load_model
 
-REF = "/root/reference/dial_mpc/models"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mjcf_compiled.npz")
 
 
 def test_go2_counts_and_constants():
@@ -51,11 +51,15 @@ def test_h1_counts():
     assert np.allclose(m["con_solimp"][0], [0.9, 0.95, 0.001, 0.5, 2.0]) and np.allclose(m["con_margin"], 0)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
 @pytest.mark.parametrize("robot,xml", [("unitree_go2", "mjx_scene_force.xml"), ("unitree_h1", "mjx_scene_h1_walk.xml"),
                                        ("unitree_go2", "mjx_scene_force_crate.xml"), ("unitree_h1", "mjx_scene_h1_push_crate.xml")])
 def test_shipped_json_matches_fresh_compile(robot, xml):
-    fresh = mjcf.compile_mjcf(os.path.join(REF, robot, xml))
+    """Every array of the compiled upstream scene, bit for bit, in the shipped JSON.  The XML files are not part of this
+    repository: their compiled arrays are stored in tests/golden/mjcf_compiled.npz (tools/compile_models.py --golden)."""
+    prefix = f"{robot}__{os.path.splitext(xml)[0]}__"
+    with np.load(GOLDEN) as g:
+        fresh = {k[len(prefix):]: g[k] for k in g.files if k.startswith(prefix)}
+    assert len(fresh) >= 60, sorted(fresh)
     shipped = load_model(robot, xml)
     for k, v in fresh.items():
         if isinstance(v, np.ndarray):
