@@ -161,6 +161,14 @@ def load(path: Optional[str] = None):
             raise
     lib.dial_shift.argtypes = [vp, fp, vp]
     lib.dial_env_step.argtypes = [vp, fp, fp, fp, fp, fp, vp]
+    try:
+        lib.dial_reverse_once_batch.argtypes = [vp, fp, fp, fp, ci, fp, ci, fp, fp, fp, fp, fp, vp]
+        lib.dial_reverse_once_batch_rng.argtypes = [vp, fp, fp, fp, ci, u64, u32, ci, fp, fp, fp, fp, fp, vp]
+        lib.dial_shift_batch.argtypes = [vp, fp, ci, vp]
+        lib.dial_env_step_batch.argtypes = [vp, fp, fp, fp, fp, fp, ci, vp]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack the grouped entry points)
+            raise
     lib.dial_env_reset.argtypes = [vp, fp, fp, fp, fp, fp, vp]
     lib.dial_env_reset_batch.argtypes = [vp, fp, fp, fp, fp, fp, ci, vp]
     lib.dial_status.argtypes = [vp]
@@ -180,7 +188,8 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
             "dial_shard_rollout", "dial_shard_reduce", "dial_shard_ybar", "dial_reverse_once_rng",
             "dial_shard_rollout_rng", "dial_rng_fill", "dial_shard_ybar_rng", "dial_shard_pack_rewards",
             "dial_shard_ybar_gathered", "dial_shard_ybar_gathered_rng", "dial_shard_reduce_gathered", "dial_shift", "dial_env_step", "dial_env_reset", "dial_env_reset_batch",
-            "dial_status", "dial_set_timing", "dial_get_rollout_ms", "dial_abi_sizes")
+            "dial_status", "dial_set_timing", "dial_get_rollout_ms", "dial_abi_sizes",
+            "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch")
 
 
 def _ptr(t) -> Optional[int]:
@@ -217,6 +226,7 @@ class Context:
         self.state_size = _abi.state_size(model.nq, model.nv)
         h = ctypes.c_void_p()
         self.options = dict(options or {})
+        self.plan_cap = max(1, int(self.options.get("plan_cap", 0)))   # plans of one grouped call (reverse_once_batch)
         unknown = set(self.options) - set(_abi.DialOptions._meta)
         if unknown:
             raise ValueError(f"unknown dial_options fields: {sorted(unknown)}")
@@ -258,6 +268,20 @@ class Context:
         self._check(self.lib.dial_env_reset_batch(self.h, _ptr(qpos), _ptr(qvel), _ptr(states), None, None, n, _stream()),
                     "dial_env_reset_batch")
         return states
+
+    def env_step_batch(self, states, actions):
+        """M states in one launch: states [M, state_size], actions [M, nu] -> (states, xpos [M, nbody-1, 3], xquat, ctrl [M, nu])."""
+        import torch
+        M = int(states.shape[0])
+        assert tuple(states.shape) == (M, self.state_size) and tuple(actions.shape) == (M, self.nu)
+        states = states.clone()
+        f32 = dict(dtype=torch.float32, device=self.torch_device)
+        xpos = torch.zeros((M, self.nbody - 1, 3), **f32)
+        xquat = torch.zeros((M, self.nbody - 1, 4), **f32)
+        ctrl = torch.zeros((M, self.nu), **f32)
+        self._check(self.lib.dial_env_step_batch(self.h, _ptr(states), _ptr(actions), _ptr(xpos), _ptr(xquat), _ptr(ctrl), M,
+                                                 _stream()), "dial_env_step_batch")
+        return states, xpos, xquat, ctrl
 
     def env_step(self, state, action):
         import torch
@@ -316,6 +340,47 @@ class Context:
                                                    _ptr(out["rews"]), _ptr(out["qbar"]), _ptr(out["qdbar"]),
                                                    _ptr(out["xbar"]), _stream()), "dial_reverse_once_rng")
         return out
+
+    # ---- grouped planning: M plans in one launch (dial_reverse_once_batch; plan g = row g of every argument)
+    def _out_batch(self, M: int, want_bars: bool):
+        import torch
+        cfg = self.cfg
+        N, Hn1, T = cfg.Nsample, cfg.Hnode + 1, cfg.Hsample + 1
+        f32 = dict(dtype=torch.float32, device=self.torch_device)
+        return dict(Ybar=torch.empty((M, Hn1, self.nu), **f32), rews=torch.empty((M, N + 1), **f32),
+                    qbar=torch.empty((M, T, self.nq), **f32) if want_bars else None,
+                    qdbar=torch.empty((M, T, self.nv), **f32) if want_bars else None,
+                    xbar=torch.empty((M, T, self.nx), **f32) if want_bars else None)
+
+    def reverse_once_batch(self, states, Ybars, noise_scales, eps, out=None, want_bars: bool = True):
+        """states [M, state_size], Ybars [M, Hn1, nu], noise_scales [M, ns], eps [M, N, Hn1, nu] -> dict of [M, ...] outputs."""
+        M = int(states.shape[0])
+        N, Hn1 = self.cfg.Nsample, self.cfg.Hnode + 1
+        assert tuple(eps.shape) == (M, N, Hn1, self.nu) and tuple(Ybars.shape) == (M, Hn1, self.nu)
+        if out is None:
+            out = self._out_batch(M, want_bars)
+        self._check(self.lib.dial_reverse_once_batch(self.h, _ptr(states), _ptr(Ybars), _ptr(noise_scales),
+                                                     int(noise_scales.shape[-1]), _ptr(eps), M, _ptr(out["Ybar"]), _ptr(out["rews"]),
+                                                     _ptr(out["qbar"]), _ptr(out["qdbar"]), _ptr(out["xbar"]), _stream()),
+                    "dial_reverse_once_batch")
+        return out
+
+    def reverse_once_batch_rng(self, states, Ybars, noise_scales, seed: int, counter: int, out=None, want_bars: bool = True):
+        """reverse_once_batch with in-kernel noise: plan g draws rows [g N, (g + 1) N) of rng_fill(seed, counter, 0, M N)."""
+        M = int(states.shape[0])
+        if out is None:
+            out = self._out_batch(M, want_bars)
+        self._check(self.lib.dial_reverse_once_batch_rng(self.h, _ptr(states), _ptr(Ybars), _ptr(noise_scales),
+                                                         int(noise_scales.shape[-1]), int(seed), int(counter), M, _ptr(out["Ybar"]),
+                                                         _ptr(out["rews"]), _ptr(out["qbar"]), _ptr(out["qdbar"]), _ptr(out["xbar"]),
+                                                         _stream()), "dial_reverse_once_batch_rng")
+        return out
+
+    def shift_batch(self, Y):
+        """Y [M, Hn1, nu] -> shifted copy (one launch)."""
+        Y = Y.clone()
+        self._check(self.lib.dial_shift_batch(self.h, _ptr(Y), int(Y.shape[0]), _stream()), "dial_shift_batch")
+        return Y
 
     def rng_fill(self, seed: int, counter: int, n_begin: int, n_count: int):
         import torch

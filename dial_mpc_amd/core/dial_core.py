@@ -39,11 +39,12 @@ def softmax_update(weights, Y0s, sigma, mu_0t):
 
 class MBDPI:
     def __init__(self, args: DialConfig, env, device: Optional[int] = None, kernel_rng: bool = False,
-                 force_sharded: bool = False, options: Optional[dict] = None):
+                 force_sharded: bool = False, options: Optional[dict] = None, n_plans: int = 1):
         """kernel_rng=True: the noise is generated inside the rollout kernel (Philox keyed by args.seed and a call
         counter) instead of by torch.randn -- the production setting; parity runs pass `eps` explicitly.
         force_sharded (measurement hook): run the sharded code path, collectives included, on a 1-rank process group.
-        options: `dial_options` fields for the context (launch-shape / measurement switches, include/dial_mpc.h)."""
+        options: `dial_options` fields for the context (launch-shape / measurement switches, include/dial_mpc.h).
+        n_plans: plans one reverse_once_batch call may carry (the context's dial_options.plan_cap)."""
         import torch
         self.kernel_rng = bool(kernel_rng)
         self._rng_counter = 0
@@ -72,6 +73,11 @@ class MBDPI:
             pass
         from dial_mpc_amd.core.sharding import partition
         self._per, self.n_begin, self.n_local = partition(args.Nsample, self.rank, self.world)
+        if int(n_plans) < 1:
+            raise ValueError("n_plans must be >= 1")
+        self.n_plans = int(n_plans)
+        if self.n_plans > 1:
+            options = dict(options or {}, plan_cap=self.n_plans)
         # a rank's rollout scratch is sized by its own shard, not by the global sample count
         self.ctx = _lib.Context(env.make_model(), env.make_task(), self.cfg, device,
                                 n_local_cap=None if self.world == 1 else self._per, options=options)
@@ -169,6 +175,47 @@ class MBDPI:
                                     self.args.Hnode + 1, packed, Ybar_i, noise_scale,
                                     eps.contiguous() if eps is not None else None, want_bars, plan=self._plan, rng=rng)
 
+    # ---- M independent plans in one launch: jax.vmap(reverse_once) over (state, rng, Ybar_i, noise_scale)
+    def reverse_once_batch(self, states, rng, Ybars, noise_scales, eps=None, want_bars: bool = True):
+        """states: list of M States or packed [M, state_size]; Ybars [M, Hnode+1, nu]; noise_scales [M, ns] (or [ns]: the same for all).
+        eps [M, N, Hnode+1, nu] explicit noise; None: kernel_rng -> in-kernel Philox (plan g draws global samples g N ..), else
+        torch.randn from `rng`.  Returns (rng, Ybar [M, Hnode+1, nu], info) with info rews [M, N+1], qbar / qdbar [M, T, .],
+        xbar [M, T, nbody-1, 3] (None with want_bars=False) and new_noise_scale."""
+        import torch
+        if self.world > 1 or self._force_sharded:
+            raise NotImplementedError("reverse_once_batch: grouped plans run on one rank (sharded batches are not supported)")
+        if isinstance(states, (list, tuple)):
+            states = torch.stack([_packed(st) for st in states])
+        states = torch.as_tensor(states, dtype=torch.float32, device=self.device).contiguous()
+        M = int(states.shape[0])
+        Ybars = torch.as_tensor(Ybars, dtype=torch.float32, device=self.device).contiguous()
+        nsc = torch.as_tensor(noise_scales, dtype=torch.float32, device=self.device)
+        if nsc.dim() < 2:
+            nsc = nsc.reshape(1, -1).expand(M, -1)
+        nsc = nsc.reshape(M, -1).contiguous()
+        T, nb1 = self.args.Hsample + 1, self.ctx.nbody - 1
+        if eps is None and self.kernel_rng:
+            counter = self._rng_counter
+            self._rng_counter += 1
+            out = self.ctx.reverse_once_batch_rng(states, Ybars, nsc, int(self.args.seed), counter, want_bars=want_bars)
+        else:
+            if eps is None:
+                gen = _generator(rng, self.device)
+                eps = torch.randn((M, self.args.Nsample, self.args.Hnode + 1, self.nu), generator=gen, device=self.device,
+                                  dtype=torch.float32)
+                rng = gen
+            out = self.ctx.reverse_once_batch(states, Ybars, nsc, eps.contiguous(), want_bars=want_bars)
+        xbar = out["xbar"]
+        info = {"rews": out["rews"], "qbar": out["qbar"], "qdbar": out["qdbar"],
+                "xbar": xbar.reshape(M, T, nb1, 3) if xbar is not None else None, "new_noise_scale": nsc}
+        return rng, out["Ybar"], info
+
+    def shift_batch(self, Ys):
+        """shift of M plans in one launch: Ys [M, Hnode+1, nu]."""
+        import torch
+        Ys = torch.as_tensor(Ys, dtype=torch.float32, device=self.device).contiguous()
+        return self.ctx.shift_batch(Ys)
+
     # ---- receding-horizon shift (dial_core.py:160-172)
     def shift(self, Y):
         import torch
@@ -206,8 +253,16 @@ def load_dial_and_env(config_dict: Dict[str, Any]):
     return dial_config, env_config, env
 
 
-def main():
-    """Synchronous simulation driver: the body of the reference's ``main`` (dial_core.py:175-329)."""
+def _positive_int(v: str) -> int:
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"must be >= 1, got {v}")
+    return n
+
+
+def main(argv=None):
+    """Synchronous simulation driver: the body of the reference's ``main`` (dial_core.py:175-329).
+    ``--n-envs M`` (M > 1) runs M closed loops through the grouped entry points (main_batched)."""
     import torch
     import yaml
     from dial_mpc_amd.examples import examples
@@ -220,7 +275,9 @@ def main():
     group.add_argument("--list-examples", action="store_true")
     parser.add_argument("--custom-env", type=str, default=None, help="Custom environment to import dynamically")
     parser.add_argument("--n-steps", type=int, default=None, help="override n_steps from the YAML")
-    args = parser.parse_args()
+    parser.add_argument("--n-envs", type=_positive_int, default=1,
+                        help="M closed loops from env.reset, planned together in one launch per iteration (default 1)")
+    args = parser.parse_args(argv)
 
     if args.list_examples:
         print("Examples:")
@@ -237,6 +294,8 @@ def main():
     dial_config, env_config, env = load_dial_and_env(config_dict)
     if args.n_steps is not None:
         dial_config.n_steps = args.n_steps
+    if args.n_envs > 1:
+        return main_batched(dial_config, env, args.n_envs)
     print("Creating environment")
     mbdpi = MBDPI(dial_config, env)
     rng = _generator(dial_config.seed, mbdpi.device)
@@ -273,6 +332,58 @@ def main():
     states_arr, pred_arr = result_arrays(rollout, infos)
     np.save(os.path.join(dial_config.output_dir, f"{timestamp}_states"), states_arr)
     np.save(os.path.join(dial_config.output_dir, f"{timestamp}_predictions"), pred_arr)
+
+
+def batched_loop(mbdpi: "MBDPI", env, states, n_steps: int, eps_fn=None, on_tick=None):
+    """M closed loops of the synchronous driver, planned together: per tick env.step of all M states (one launch), shift of all M
+    plans, then Ndiffuse grouped annealing iterations.  eps_fn(t, i) -> eps [M, N, Hnode+1, nu] or None (noise from the planner's rng
+    / kernel_rng).  Returns (rollouts: per tick the list of M States, infos: per tick the last iteration's info, tick ms)."""
+    import torch
+    dc = mbdpi.args
+    M = len(states)
+    rng = _generator(dc.seed, mbdpi.device)
+    Y0 = torch.zeros((M, dc.Hnode + 1, mbdpi.nu), dtype=torch.float32, device=mbdpi.device)
+    rollouts, infos, tick_ms = [], [], []
+    for t in range(n_steps):
+        states = env.step_batch(states, Y0[:, 0])
+        rollouts.append(states)
+        t0 = time.time()
+        Y0 = mbdpi.shift_batch(Y0)
+        n_diffuse = dc.Ndiffuse_init if t == 0 else dc.Ndiffuse
+        factors = mbdpi.sigma_control[None, :] * (dc.traj_diffuse_factor ** torch.arange(n_diffuse, device=mbdpi.device))[:, None]
+        info = None
+        for i in range(n_diffuse):
+            eps = eps_fn(t, i) if eps_fn is not None else None
+            rng, Y0, info = mbdpi.reverse_once_batch(states, rng, Y0, factors[i], eps=eps, want_bars=(i == n_diffuse - 1))
+        torch.cuda.synchronize()
+        mbdpi.ctx.status()
+        tick_ms.append((time.time() - t0) * 1e3)
+        infos.append(info)
+        if on_tick is not None:
+            on_tick(t, states, tick_ms[-1])
+    return rollouts, infos, tick_ms
+
+
+def main_batched(dial_config, env, n_envs: int):
+    """``--n-envs M``: M closed loops from env.reset, each with its own plan noise, planned in one launch per annealing iteration."""
+    print(f"Creating environment ({n_envs} closed loops, planned together)")
+    mbdpi = MBDPI(dial_config, env, n_plans=n_envs)
+    states = [env.reset() for _ in range(n_envs)]
+
+    def on_tick(t, sts, ms):
+        if t % 20 == 0:
+            print(f"step {t:4d}  rew {[round(float(s.reward), 3) for s in sts]}  tick {ms:.2f} ms")
+    rollouts, infos, tick_ms = batched_loop(mbdpi, env, states, dial_config.n_steps, on_tick=on_tick)
+    for e in range(n_envs):
+        print(f"env {e}: mean reward = {np.mean([float(r[e].reward) for r in rollouts]):.2e}")
+    if len(tick_ms) > 1:
+        print(f"batched tick (shift + Ndiffuse iterations, {n_envs} plans) p50 = {np.percentile(tick_ms[1:], 50):.3f} ms, "
+              f"p95 = {np.percentile(tick_ms[1:], 95):.3f} ms")
+    os.makedirs(dial_config.output_dir, exist_ok=True)
+    timestamp = time.strftime("%Y%m%d-%H%M%S")
+    per_env = [result_arrays([r[e] for r in rollouts], [{"xbar": inf["xbar"][e]} for inf in infos]) for e in range(n_envs)]
+    np.save(os.path.join(dial_config.output_dir, f"{timestamp}_states"), np.stack([p[0] for p in per_env]))
+    np.save(os.path.join(dial_config.output_dir, f"{timestamp}_predictions"), np.stack([p[1] for p in per_env]))
 
 
 def result_arrays(rollout, infos):

@@ -7,10 +7,10 @@
 //                    chip is decided in launch_rollout(): rollout queue (batch > resident set), mean-trajectory
 //                    relay (one-wavefront workgroups, N a multiple of the SIMD count), split launch (H1 / Allegro
 //                    at N = 8 x CUs); every wavefront re-draws its issue priority (wave.h: redraw_priority).
-//   weights_kernel   K4a: rew_bar, std, softmax over all N+1 mean rewards (one workgroup, fixed
+//   weights_kernel   K4a: rew_bar, std, softmax over all N+1 mean rewards (one workgroup per plan, fixed
 //                    reduction order => bit-identical on every GPU of a sharded run).
-//   wsum_*_kernel    K4b: weighted means of Y0s / q / qd / x.pos, two deterministic passes.
-//   shift_kernel     K5, env_step_kernel / env_reset_kernel  K6 (B = 1).
+//   wsum_*_kernel    K4b: weighted means of Y0s / q / qd / x.pos, two deterministic passes (plan on grid.z).
+//   shift_kernel     K5, env_step_kernel / env_reset_kernel  K6 (one workgroup per state / plan).
 // There is no CPU fallback: every entry point needs a HIP device and fails with DIAL_ERR_HIP otherwise.
 #include <hip/hip_runtime.h>
 
@@ -94,12 +94,15 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 // `gathered` != nullptr (sharded runs): the rewards arrive as the all-gather delivered them -- [world][per + 1]: every rank's noisy
 // samples, then its copy of the mean-trajectory reward -- and are put into the order K4 wants ([n_total noisy | mean], written to
 // `rews_out`) by this kernel's first pass: the packing launch of rounds 2-5 (dial_shard_pack_rewards) is gone from the iteration.
+// Grouped launches (dial_reverse_once_batch): workgroup g forms the softmax of plan g -- rews_in / weights [plans][B]; every other
+// launch has one workgroup (the gathered path only ever runs that way).
 extern "C" __global__ void __launch_bounds__(WK_THREADS)
 weights_kernel(const float* __restrict__ rews_in, int B, float temp, float* __restrict__ weights, const float* __restrict__ gathered,
                int per, float* __restrict__ rews_out) {
   __shared__ float red[WK_THREADS / 64];
   const int tid = threadIdx.x;
-  const float* rews = rews_in;
+  const float* rews = rews_in + (size_t)blockIdx.x * B;
+  weights += (size_t)blockIdx.x * B;
   if (gathered) {
     const int n_total = B - 1;
     for (int n = tid; n < B; n += WK_THREADS)
@@ -162,7 +165,8 @@ weights_kernel(const float* __restrict__ rews_in, int B, float temp, float* __re
 
 // K4b (dial_core.py:132-135): out[c] = sum_n w[widx(n)] * X_seg[n][c] over the local samples.
 struct WsumSeg { const float* X; float* out; int C; int c0; };
-struct WsumArgs { WsumSeg seg[4]; int nseg, Ctot, n_rows, w_begin, mean_row, mean_widx; };
+// plan p = blockIdx.z (grouped launches; one plan otherwise): rows of X from p x n_rows, weights from p x w_stride, out from p x C
+struct WsumArgs { WsumSeg seg[4]; int nseg, Ctot, n_rows, w_begin, mean_row, mean_widx, w_stride; };
 
 // Block = 64 columns x 4 wavefronts; wavefront g takes every 4th row of the block's row chunk, the four partial
 // sums are combined in a fixed order through LDS (deterministic, bit-identical on every rank).
@@ -174,11 +178,14 @@ wsum_partial_kernel(WsumArgs a, const float* __restrict__ weights, float* __rest
   __shared__ float red[4][64];
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + lane;
+  const int p = blockIdx.z;
+  weights += (size_t)p * a.w_stride;
+  partial += (size_t)p * WSUM_CHUNKS * a.Ctot;
   float acc = 0.f;
   if (c < a.Ctot) {
     int sg = 0;
     for (int k = 1; k < a.nseg; k++) if (c >= a.seg[k].c0) sg = k;
-    const float* X = a.seg[sg].X;
+    const float* X = a.seg[sg].X + (size_t)p * a.n_rows * a.seg[sg].C;
     const int C = a.seg[sg].C, cl = c - a.seg[sg].c0;
     const int chunk = blockIdx.y, per = (a.n_rows + WSUM_CHUNKS - 1) / WSUM_CHUNKS;
     const int r0 = chunk * per, r1 = (r0 + per < a.n_rows) ? r0 + per : a.n_rows;
@@ -198,12 +205,14 @@ extern "C" __global__ void __launch_bounds__(256)
 wsum_final_kernel(WsumArgs a, const float* __restrict__ partial) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= a.Ctot) return;
+  const int p = blockIdx.z;
+  partial += (size_t)p * WSUM_CHUNKS * a.Ctot;
   int sg = 0;
   for (int k = 1; k < a.nseg; k++) if (c >= a.seg[k].c0) sg = k;
   float acc = 0.f;
 #pragma unroll 16   // (sixteen independent loads in flight; the additions keep their order)
   for (int ch = 0; ch < WSUM_CHUNKS; ch++) acc += partial[(size_t)ch * a.Ctot + c];
-  if (a.seg[sg].out) a.seg[sg].out[c - a.seg[sg].c0] = acc;
+  if (a.seg[sg].out) a.seg[sg].out[(size_t)p * a.seg[sg].C + c - a.seg[sg].c0] = acc;
 }
 
 // Weighted mean of ALL candidate nodes, regenerated from the noise (dial_core.py:110-115,132), with a fixed reduction order
@@ -292,11 +301,12 @@ pack_rewards_kernel(const float* __restrict__ gathered, int per, int n_total, fl
   else if (n == n_total) rews_all[n] = gathered[per];   // rank 0's mean-trajectory reward (bit-identical on every rank)
 }
 
-// K5 (dial_core.py:160-166): u = W Y; u = roll(u,-1); u[-1] = 0; Y = V u.  One small workgroup.
+// K5 (dial_core.py:160-166): u = W Y; u = roll(u,-1); u[-1] = 0; Y = V u.  One small workgroup per plan (Y:[plans, Hn1, nu]).
 extern "C" __global__ void __launch_bounds__(64)
 shift_kernel(const dial_cfg* __restrict__ cfg, int nu, float* Y) {
   __shared__ float u[DIAL_MAX_T * DIAL_MAX_U];
   const int T = cfg->Hsample + 1, Hn1 = cfg->Hnode + 1;
+  Y += (size_t)blockIdx.x * Hn1 * nu;
   for (int it = threadIdx.x; it < T * nu; it += 64) {
     const int st = it / nu, a = it - st * nu;
     float acc = 0.f;
@@ -335,6 +345,7 @@ struct dial_ctx {
   int con_cap = 0, ovf_words = 0;   // generic instantiation: contact cap of the rollout kernel's LDS workspace, words of one overflow area
   float* ovf = nullptr;            // B_cap overflow areas
   int B_cap = 0, W_cap = 0, T = 0, Hn1 = 0, nx = 0;   // B_cap: rollouts this context can hold (local shard + mean), W_cap: global N + 1
+  int plan_cap = 1;            // plans of one grouped launch (dial_options.plan_cap): the rollout scratch holds plan_cap x B_cap rollouts
   float *Y0s = nullptr, *rewss = nullptr, *rews = nullptr, *qss = nullptr, *qdss = nullptr, *xss = nullptr;
   float *weights = nullptr, *partial = nullptr;
   unsigned long long* prof = nullptr;
@@ -437,6 +448,9 @@ int dial_create_ex(dial_ctx** out, const dial_model* model, const dial_task* tas
   const dial_options opt = opts ? *opts : dial_options{};
   if (opt.relay_steps < 0 || opt.relay_steps > 16) return fail(nullptr, DIAL_ERR_ARG, "dial_create_ex: options.relay_steps must be in 0 .. 16");
   if (opt.slice_steps < 0 || opt.slice_steps > 16) return fail(nullptr, DIAL_ERR_ARG, "dial_create_ex: options.slice_steps must be in 0 .. 16");
+  if (opt.plan_cap < 0 || opt.plan_cap > DIAL_MAX_PLANS) return fail(nullptr, DIAL_ERR_ARG, "dial_create_ex: options.plan_cap must be in 0 .. DIAL_MAX_PLANS");
+  if (opt.plan_cap > 1 && cfg && (long long)(cfg->Nsample + 1) * opt.plan_cap > (1LL << 30))
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_ex: options.plan_cap x (Nsample + 1) exceeds 2^30 rollouts");
   *out = nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -492,6 +506,7 @@ int dial_create_ex(dial_ctx** out, const dial_model* model, const dial_task* tas
   dial_ctx* ctx = new dial_ctx();
   ctx->device = device;
   ctx->opt = opt;
+  ctx->plan_cap = opt.plan_cap > 1 ? opt.plan_cap : 1;
   ctx->hm = *model;
   ctx->ht = *task;
   int rc = dial_build_derived(model, &ctx->hd);
@@ -715,7 +730,8 @@ int dial_create_ex(dial_ctx** out, const dial_model* model, const dial_task* tas
     ctx->W_cap = cfg->Nsample + 1;
     // one overflow area per wavefront slot of the LARGEST grid this context launches: B_cap rollouts, or B_cap - 1 noisy
     // ones + the relay pieces of the mean trajectory (at most Hsample + 1 of them) -- launch_rollout checks the grid
-    ctx->ovf_slots = ctx->B_cap + (cfg->Hsample + 1 > 16 ? cfg->Hsample + 1 : 16);   // (and a last workgroup of up to 9 wavefronts)
+    // (grouped launches: plan_cap x B_cap rollouts, no relay)
+    ctx->ovf_slots = ctx->plan_cap * ctx->B_cap + (cfg->Hsample + 1 > 16 ? cfg->Hsample + 1 : 16);   // (and a last workgroup of up to 9 wavefronts)
     if (ctx->con_cap > 0) HIP_TRY_CREATE(hipMalloc(&ctx->ovf, (size_t)ctx->ovf_slots * ctx->ovf_words * sizeof(float)));
     ctx->T = cfg->Hsample + 1;
     ctx->Hn1 = cfg->Hnode + 1;
@@ -724,15 +740,16 @@ int dial_create_ex(dial_ctx** out, const dial_model* model, const dial_task* tas
     // resident set.  (Not for the Go2's large batches: one hand-over per rollout and piece through global memory -- 4096 release /
     // acquire pairs per piece level -- cost more than the lone last rollout it would hide: N = 4096 1.34 vs 0.80 ms,
     // profiles/r04_ab_call_v_sliced_go2_k2_crate_quad.txt; those batches interleave the mean trajectory instead, see launch_rollout.)
-    if (ctx->inst == 4 && !opt.no_slice && ctx->resident_blocks > 0 && ctx->B_cap > ctx->resident_blocks * ctx->wpb) {
+    const int B_all = ctx->plan_cap * ctx->B_cap;   // rollouts of the largest launch (grouped: plan_cap plans)
+    if (ctx->inst == 4 && !opt.no_slice && ctx->resident_blocks > 0 && B_all > ctx->resident_blocks * ctx->wpb) {
       ctx->slice_stride = model->nq + 2 * model->nv + DIAL_INFO_N + 4;
-      ctx->slice_cap = ctx->B_cap;
+      ctx->slice_cap = B_all;
       if (opt.slice_steps >= 1) ctx->slice_steps = opt.slice_steps;
-      HIP_TRY_CREATE(hipMalloc(&ctx->slice_buf, sizeof(float) * (size_t)ctx->slice_stride * ctx->B_cap));
-      HIP_TRY_CREATE(hipMalloc(&ctx->slice_flag, sizeof(int) * (size_t)ctx->B_cap));
-      HIP_TRY_CREATE(hipMemset(ctx->slice_flag, 0, sizeof(int) * (size_t)ctx->B_cap));
+      HIP_TRY_CREATE(hipMalloc(&ctx->slice_buf, sizeof(float) * (size_t)ctx->slice_stride * B_all));
+      HIP_TRY_CREATE(hipMalloc(&ctx->slice_flag, sizeof(int) * (size_t)B_all));
+      HIP_TRY_CREATE(hipMemset(ctx->slice_flag, 0, sizeof(int) * (size_t)B_all));
     }
-    const size_t B = ctx->B_cap, T = ctx->T;
+    const size_t B = B_all, T = ctx->T;
     HIP_TRY_CREATE(hipMalloc(&ctx->dcfg, sizeof(dial_cfg)));
     HIP_TRY_CREATE(hipMemcpy(ctx->dcfg, cfg, sizeof(dial_cfg), hipMemcpyHostToDevice));
     HIP_TRY_CREATE(hipMalloc(&ctx->Y0s, sizeof(float) * B * ctx->Hn1 * model->nu));
@@ -741,11 +758,11 @@ int dial_create_ex(dial_ctx** out, const dial_model* model, const dial_task* tas
     HIP_TRY_CREATE(hipMalloc(&ctx->qss, sizeof(float) * B * T * model->nq));
     HIP_TRY_CREATE(hipMalloc(&ctx->qdss, sizeof(float) * B * T * model->nv));
     HIP_TRY_CREATE(hipMalloc(&ctx->xss, sizeof(float) * B * T * ctx->nx));
-    HIP_TRY_CREATE(hipMalloc(&ctx->weights, sizeof(float) * ctx->W_cap));
+    HIP_TRY_CREATE(hipMalloc(&ctx->weights, sizeof(float) * ctx->W_cap * ctx->plan_cap));
     const size_t Ctot = (size_t)ctx->Hn1 * model->nu + T * (model->nq + model->nv + ctx->nx);
     // K4b's partial sums: [chunk][Ctot] (wsum_partial_kernel) or the mean-action kernel's [YB_CHUNKS][C] (ybar_partial_kernel), whichever is larger
     const size_t part_w = ((Ctot + 63) / 64) * (size_t)WSUM_CHUNKS * 64, part_y = (((size_t)ctx->Hn1 * model->nu + 63) / 64) * (size_t)YB_CHUNKS_HOST * 64;
-    HIP_TRY_CREATE(hipMalloc(&ctx->partial, sizeof(float) * (part_w > part_y ? part_w : part_y)));
+    HIP_TRY_CREATE(hipMalloc(&ctx->partial, sizeof(float) * (part_w * ctx->plan_cap > part_y ? part_w * ctx->plan_cap : part_y)));
     // 32 section / event counters + (profile builds) a start / end timestamp per rollout of the last launch
     HIP_TRY_CREATE(hipMalloc(&ctx->prof, sizeof(unsigned long long) * (32 + 6 * B)));
     HIP_TRY_CREATE(hipMemset(ctx->prof, 0, sizeof(unsigned long long) * (32 + 6 * B)));
@@ -832,7 +849,7 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
   // (profiles/r05_ab_pair_kernel.txt, profiles/r05_sections_pair_cycles.txt)
   if (ctx->pair_ok && !tracing && (ctx->opt.pair_mode == 2 || B > DIAL_GO2_PAIR_MIN_B)) {
     dial::RolloutIO io = io_in;
-    const bool mean_last = !io.us && io.n_noise == B - 1 && ((B - 1) & 1) == 0 && ctx->relay_buf && ctx->relay_flag && !ctx->no_mean_inline;
+    const bool mean_last = !io.us && !io.plan_rollouts && io.n_noise == B - 1 && ((B - 1) & 1) == 0 && ctx->relay_buf && ctx->relay_flag && !ctx->no_mean_inline;
     if ((B + 1) / 2 <= ctx->resident_pair || opt_no_queue(ctx)) {
       // plain grid: wavefront p runs rollouts 2 p, 2 p + 1 (the mean trajectory alone in the last one).  The interleaved mean
       // trajectory was measured here as well (N = 2048 as exactly 1024 wavefronts, one per SIMD): 0.418 ms against 0.389 ms with
@@ -869,8 +886,10 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
   io.con_cap = ctx->ovf ? ctx->con_cap : 0;
   io.ovf = ctx->ovf;
   io.ovf_words = ctx->ovf_words;
-  // (only when the noisy rollouts fill the SIMDs evenly and the mean trajectory is the odd one out: N = k x 1024)
-  if (ctx->relay_ok && !large && !io.us && io.n_noise == B - 1 && B > 1 && ctx->T >= 4 && ctx->n_simd > 0 &&
+  // (only when the noisy rollouts fill the SIMDs evenly and the mean trajectory is the odd one out: N = k x 1024; never in grouped
+  //  launches, whose mean trajectories are rollouts N, 2 N + 1, ...: they -- and the interleaved mean trajectory, the split launch -- take
+  //  the paths that treat every rollout alike)
+  if (ctx->relay_ok && !large && !io.us && !io.plan_rollouts && io.n_noise == B - 1 && B > 1 && ctx->T >= 4 && ctx->n_simd > 0 &&
       ((B - 1) % ctx->n_simd == 0 || ctx->relay_always)) {
     const int pieces = (ctx->T + ctx->relay_steps - 1) / ctx->relay_steps;
     if ((B - 1) + pieces <= ctx->resident_blocks) {
@@ -898,7 +917,7 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
     HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)next, blocks * wpb, 1, st));
     // Go2's large batches whose last rollout is the mean trajectory: it is not a queue item -- the first T wavefronts of the
     // launch run one step of it each between two steps of their own (rollout_driver.h: mean_inline)
-    if (large && !ctx->no_mean_inline && !io.us && io.n_noise == B - 1 && ctx->T <= blocks * wpb && io.relay_stride == 0) {
+    if (large && !ctx->no_mean_inline && !io.us && !io.plan_rollouts && io.n_noise == B - 1 && ctx->T <= blocks * wpb && io.relay_stride == 0) {
       io.mean_inline = 1;
       io.relay_buf = ctx->relay_buf;
       io.relay_flag = ctx->relay_flag;
@@ -928,7 +947,7 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
   // Batch = 8 x CUs + 1 (N = 2048 on 256 CUs) with multi-wavefront workgroups: the N noisy rollouts as evenly sized
   // workgroups that load every CU with 8 wavefronts (Allegro: one workgroup of 8, H1: two of 4, one wavefront per SIMD
   // each), the mean trajectory as a one-wavefront workgroup launched on the side stream (fork / join by events)
-  if (ctx->split_ok && !tracing && !next && !io.us && io.n_noise == B - 1 && (B - 1) == 8 * (ctx->n_simd / 4)) {
+  if (ctx->split_ok && !tracing && !next && !io.us && !io.plan_rollouts && io.n_noise == B - 1 && (B - 1) == 8 * (ctx->n_simd / 4)) {
     HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
     dial::RolloutIO io1 = io;
@@ -1049,8 +1068,9 @@ int dial_rng_fill(dial_ctx* ctx, uint64_t seed, uint32_t counter, int n_begin, i
   return DIAL_OK;
 }
 
+// plans > 1 (grouped launches): plan p's rows start at p x n_rows of the scratch, its weights at p x n_rows, its outputs at p x C
 static int launch_wsum(dial_ctx* ctx, const float* weights, int n_rows, int w_begin, int mean_row, int mean_widx,
-                       float* Yo, float* qo, float* qdo, float* xo, hipStream_t st, bool nodes_only = false) {
+                       float* Yo, float* qo, float* qdo, float* xo, hipStream_t st, bool nodes_only = false, int plans = 1) {
   const dial_model& m = ctx->hm;
   WsumArgs a;
   const int T = ctx->T;
@@ -1061,9 +1081,10 @@ static int launch_wsum(dial_ctx* ctx, const float* weights, int n_rows, int w_be
   a.seg[3] = {ctx->xss, xo, T * ctx->nx, a.seg[2].c0 + a.seg[2].C};
   a.Ctot = nodes_only ? a.seg[0].C : a.seg[3].c0 + a.seg[3].C;
   a.n_rows = n_rows; a.w_begin = w_begin; a.mean_row = mean_row; a.mean_widx = mean_widx;
+  a.w_stride = plans > 1 ? n_rows : 0;
   const int gx = (a.Ctot + 255) / 256;
-  hipLaunchKernelGGL(wsum_partial_kernel, dim3((a.Ctot + 63) / 64, WSUM_CHUNKS), dim3(256), 0, st, a, weights, ctx->partial);
-  hipLaunchKernelGGL(wsum_final_kernel, dim3(gx), dim3(256), 0, st, a, (const float*)ctx->partial);
+  hipLaunchKernelGGL(wsum_partial_kernel, dim3((a.Ctot + 63) / 64, WSUM_CHUNKS, plans), dim3(256), 0, st, a, weights, ctx->partial);
+  hipLaunchKernelGGL(wsum_final_kernel, dim3(gx, 1, plans), dim3(256), 0, st, a, (const float*)ctx->partial);
   HIP_TRY(ctx, hipGetLastError());
   return DIAL_OK;
 }
@@ -1192,6 +1213,58 @@ int dial_reverse_once_rng(dial_ctx* ctx, const float* state, const float* Ybar_i
                            xbar, stream, "dial_reverse_once_rng");
 }
 
+// Grouped planning: M plans of one context in one rollout launch + one K4a + one K4b pair.  Plan g, sample n is batch rollout
+// g (N + 1) + n, row g (N + 1) + N its mean trajectory; M = 1 is exactly reverse_once (same launch, same paths).
+static int reverse_once_batch_impl(dial_ctx* ctx, const float* states, const float* Ybar_in, const float* noise_scale, int ns,
+                                   const float* eps, int use_rng, uint64_t seed, uint32_t counter, int M, float* Ybar_out,
+                                   float* rews, float* qbar, float* qdbar, float* xbar, void* stream, const char* who) {
+  if (!ctx) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": null context");
+  if (!ctx->has_cfg) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": context was created without a dial_cfg");
+  if (M < 1 || M > ctx->plan_cap)
+    return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": M = " + std::to_string(M) + " plans is outside 1 .. the context's plan capacity " +
+                                   std::to_string(ctx->plan_cap) + " (dial_options.plan_cap)");
+  const int N = ctx->hc.Nsample;
+  if (ctx->B_cap < N + 1) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": the context is sharded (n_local_cap < Nsample); grouped plans need the whole batch");
+  if (ns != 1 && ns != ctx->Hn1) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": ns = " + std::to_string(ns) + " must be 1 or Hnode+1 = " + std::to_string(ctx->Hn1));
+  if (!states || !Ybar_in || !noise_scale || (!eps && !use_rng) || !Ybar_out || !rews) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": null argument");
+  if (M == 1)
+    return reverse_once_impl(ctx, states, Ybar_in, noise_scale, ns, eps, use_rng, seed, counter, Ybar_out, rews, qbar, qdbar, xbar, stream, who);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const bool bars = qbar || qdbar || xbar;
+  const int B = M * (N + 1);
+  dial::RolloutIO io{states, nullptr, eps, Ybar_in, noise_scale, ns, N, ctx->T, ctx->Hn1,
+                     ctx->Y0s, ctx->rewss, rews, bars ? ctx->qss : nullptr, bars ? ctx->qdss : nullptr,   // (lean: K4b sums the nodes alone)
+                     bars ? ctx->xss : nullptr, ctx->prof, use_rng, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), counter, 0};
+  io.plan_rollouts = N + 1;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = launch_rollout(ctx, io, B, st)) return rc;
+  hipLaunchKernelGGL(weights_kernel, dim3(M), dim3(WK_THREADS), 0, st, (const float*)rews, N + 1, ctx->hc.temp_sample, ctx->weights, (const float*)nullptr, 0, (float*)nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  return launch_wsum(ctx, ctx->weights, N + 1, 0, N, N, Ybar_out, qbar, qdbar, xbar, st, !bars, M);
+}
+
+int dial_reverse_once_batch(dial_ctx* ctx, const float* states, const float* Ybar_in, const float* noise_scale, int ns, const float* eps,
+                            int M, float* Ybar_out, float* rews, float* qbar, float* qdbar, float* xbar, void* stream) {
+  return reverse_once_batch_impl(ctx, states, Ybar_in, noise_scale, ns, eps, 0, 0, 0, M, Ybar_out, rews, qbar, qdbar, xbar, stream,
+                                 "dial_reverse_once_batch");
+}
+
+int dial_reverse_once_batch_rng(dial_ctx* ctx, const float* states, const float* Ybar_in, const float* noise_scale, int ns,
+                                uint64_t seed, uint32_t counter, int M, float* Ybar_out, float* rews, float* qbar, float* qdbar,
+                                float* xbar, void* stream) {
+  return reverse_once_batch_impl(ctx, states, Ybar_in, noise_scale, ns, nullptr, 1, seed, counter, M, Ybar_out, rews, qbar, qdbar, xbar,
+                                 stream, "dial_reverse_once_batch_rng");
+}
+
+int dial_shift_batch(dial_ctx* ctx, float* Y, int M, void* stream) {
+  if (!ctx || !Y || M < 1) return fail(ctx, DIAL_ERR_ARG, "dial_shift_batch: null argument or M < 1");
+  if (!ctx->has_cfg) return fail(ctx, DIAL_ERR_ARG, "dial_shift_batch: context was created without a dial_cfg");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(shift_kernel, dim3(M), dim3(64), 0, (hipStream_t)stream, (const dial_cfg*)ctx->dcfg, ctx->hm.nu, Y);
+  HIP_TRY(ctx, hipGetLastError());
+  return DIAL_OK;
+}
+
 int dial_shift(dial_ctx* ctx, float* Y, void* stream) {
   if (!ctx || !Y) return fail(ctx, DIAL_ERR_ARG, "dial_shift: null argument");
   if (!ctx->has_cfg) return fail(ctx, DIAL_ERR_ARG, "dial_shift: context was created without a dial_cfg");
@@ -1201,12 +1274,12 @@ int dial_shift(dial_ctx* ctx, float* Y, void* stream) {
   return DIAL_OK;
 }
 
-int dial_env_step(dial_ctx* ctx, float* state, const float* action, float* xpos_out, float* xquat_out,
-                  float* ctrl_out, void* stream) {
-  if (!ctx || !state || !action) return fail(ctx, DIAL_ERR_ARG, "dial_env_step: null argument");
+static int env_step_launch(dial_ctx* ctx, float* state, const float* action, float* xpos_out, float* xquat_out,
+                           float* ctrl_out, int n, void* stream, const char* who) {
+  if (!ctx || !state || !action || n < 1) return fail(ctx, DIAL_ERR_ARG, who);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
 #define DIAL_LAUNCH_STEP(D)                                                                                         \
-  hipLaunchKernelGGL(env_step_kernel<D>, dim3(1), dim3(64), ctx->lds_bytes, (hipStream_t)stream,                   \
+  hipLaunchKernelGGL(env_step_kernel<D>, dim3(n), dim3(64), ctx->lds_bytes, (hipStream_t)stream,                   \
                      (const CModel<D>*)ctx->dcm, (const dial_task*)ctx->dtask, state, action, xpos_out, xquat_out, \
                      ctrl_out)
   if (ctx->inst == 1) DIAL_LAUNCH_STEP(DimsGo2);
@@ -1219,6 +1292,14 @@ int dial_env_step(dial_ctx* ctx, float* state, const float* action, float* xpos_
 #undef DIAL_LAUNCH_STEP
   HIP_TRY(ctx, hipGetLastError());
   return DIAL_OK;
+}
+int dial_env_step(dial_ctx* ctx, float* state, const float* action, float* xpos_out, float* xquat_out,
+                  float* ctrl_out, void* stream) {
+  return env_step_launch(ctx, state, action, xpos_out, xquat_out, ctrl_out, 1, stream, "dial_env_step: null argument");
+}
+int dial_env_step_batch(dial_ctx* ctx, float* states, const float* actions, float* xpos_out, float* xquat_out,
+                        float* ctrl_out, int M, void* stream) {
+  return env_step_launch(ctx, states, actions, xpos_out, xquat_out, ctrl_out, M, stream, "dial_env_step_batch: null argument or M < 1");
 }
 
 static int env_reset_launch(dial_ctx* ctx, const float* qpos, const float* qvel, float* state, float* xpos_out, float* xquat_out,

@@ -94,26 +94,34 @@ DIAL_DEV void rollout_sample(W& w, const M* m, const dial_task* tg, const dial_c
   const int nstate = nq + 2 * nv + DIAL_INFO_N;
   int st_begin = 0, st_end = T;
   if (relay >= 0) { st_begin = relay * io.relay_steps; st_end = st_begin + io.relay_steps < T ? st_begin + io.relay_steps : T; }
-  if (relay <= 0) load_state(w, m, s, io.state);
+  // grouped launch (io.plan_rollouts > 0): this rollout's plan g and its index nl in the plan, once per rollout item -- wave-uniform
+  // except in the pair kernel's halves; the plan's inputs are read through them here, in the prologue only (the mean-trajectory
+  // paths inside the step loop below belong to one-plan launches).  Global noisy sample g x n_noise + nl = n - g.
+  int g = 0, nl = n;
+  if (io.plan_rollouts) { g = n / io.plan_rollouts; nl = n - g * io.plan_rollouts; }
+  const float* const Ybar = io.Ybar + (size_t)g * Hn1 * nu;
+  if (relay <= 0) load_state(w, m, s, io.state + (size_t)g * (nq + 2 * nv + DIAL_INFO_N));
   if (!io.us) {
     // K1: candidate nodes (dial_core.py:110-115)
+    const float* const nsc = io.noise_scale + g * io.ns;
+    const int ng = n - g;   // global noisy sample index (the eps row, the Philox key)
     w.items(Hn1 * nu, [&](int it) {
       const int k = it / nu, a = it - k * nu;
       float v;
-      if (n < io.n_noise) {
-        float sc = io.noise_scale[io.ns == 1 ? 0 : k];
+      if (nl < io.n_noise) {
+        float sc = nsc[io.ns == 1 ? 0 : k];
         float e;
         if (io.use_rng) {
           float z[4];
-          normal_quad((uint32_t)(io.n_offset + n), (uint32_t)(it >> 2), io.rng_iter, io.seed_lo, io.seed_hi, z);
+          normal_quad((uint32_t)(io.n_offset + ng), (uint32_t)(it >> 2), io.rng_iter, io.seed_lo, io.seed_hi, z);
           e = z[it & 3];
         } else {
-          e = io.eps[((size_t)n * Hn1 + k) * nu + a];
+          e = io.eps[((size_t)ng * Hn1 + k) * nu + a];
         }
-        v = e * sc + io.Ybar[k * nu + a];
-        if (k == 0) v = io.Ybar[a];
+        v = e * sc + Ybar[k * nu + a];
+        if (k == 0) v = Ybar[a];
       } else {
-        v = io.Ybar[k * nu + a];
+        v = Ybar[k * nu + a];
       }
       v = dm::clip(v, -1.f, 1.f);
       s.Y[it] = v;

@@ -9,11 +9,11 @@
 namespace dial {
 
 struct RolloutIO {
-  const float* state;        // packed initial state, shared by all samples
+  const float* state;        // packed initial state, shared by all samples of a plan ([plans, nstate] in grouped launches)
   const float* us;           // [B,T,nu] controls, or nullptr -> build them from nodes
-  const float* eps;          // [n_noise,Hn1,nu] standard-normal draws (nodes mode)
-  const float* Ybar;         // [Hn1,nu]
-  const float* noise_scale;  // [ns]
+  const float* eps;          // [plans * n_noise,Hn1,nu] standard-normal draws (nodes mode)
+  const float* Ybar;         // [plans,Hn1,nu]
+  const float* noise_scale;  // [plans,ns]
   int ns;
   int n_noise;               // samples with index >= n_noise roll out the mean trajectory Ybar
   int T, Hn1;
@@ -59,6 +59,11 @@ struct RolloutIO {
   // per launch), so that no wavefront slot runs two whole rollouts one after the other -- see rollout_sample
   int mean_inline;
   int spread;   // rollout_kernel.h: the spread launch (rollout index = wavefront-in-workgroup x grid + workgroup)
+  // grouped launch (dial_reverse_once_batch): rollouts per plan (n_noise noisy + the plan's mean trajectory); 0 = one plan.  Rollout n
+  // belongs to plan g = n / plan_rollouts, local index n - g x plan_rollouts; plan g reads row g of state / Ybar / noise_scale and
+  // draws the noise of global sample g x n_noise + local index (eps row, Philox key).  The plans' inputs are dense ([plans, ...]);
+  // the outputs are indexed by the batch rollout n as in one-plan launches.
+  int plan_rollouts;
 };
 
 }  // namespace dial

@@ -1,6 +1,6 @@
 // rollout_kernel.h -- the gfx950 kernels that run the per-sample body (rollout_driver.h): rollout_kernel (K1+K2+K3, one
 // wavefront per sample, 1-9 wavefronts per workgroup sharing the staged constants), env_step_kernel / env_reset_kernel
-// (K6, B = 1).  A header so that tools/isa/probe.hip can instantiate ONE kernel for ISA inspection (register / scratch /
+// (K6, one workgroup per state).  A header so that tools/isa/probe.hip can instantiate ONE kernel for ISA inspection (register / scratch /
 // spill counts) in seconds instead of building the whole library; dial_hip.hip is the only product translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -210,7 +210,11 @@ env_step_kernel(const CModel<D>* __restrict__ gm, const dial_task* __restrict__ 
   w.lane = threadIdx.x;
   w.lane_r = w.lane;
   w.launder = D::gen;
-  dial::env_step_single(w, m, tg, s, state, action, xpos_out, xquat_out, ctrl_out);
+  // (dial_env_step_batch: workgroup b steps state b of a batch -- rows of state / action / the optional outputs)
+  const int b = (int)blockIdx.x, nq = dim_nq(m), nv = dim_nv(m), nu = dim_nu(m), nb1 = dim_nb(m) - 1;
+  dial::env_step_single(w, m, tg, s, state + (size_t)b * (nq + 2 * nv + DIAL_INFO_N), action + (size_t)b * nu,
+                        xpos_out ? xpos_out + (size_t)b * nb1 * 3 : nullptr, xquat_out ? xquat_out + (size_t)b * nb1 * 4 : nullptr,
+                        ctrl_out ? ctrl_out + (size_t)b * nu : nullptr);
 }
 
 template <class D>

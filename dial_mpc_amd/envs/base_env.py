@@ -208,6 +208,16 @@ class BaseEnv:
         ctx = self._context()
         return state.stepped(ctx, action)
 
+    def step_batch(self, states, actions):
+        """env.step of M states in one launch: a list of M States and actions [M, nu] -> a list of M new States."""
+        import torch
+        from dial_mpc_amd.envs.state import State
+        ctx = self._context()
+        packed = torch.stack([st.packed for st in states]).contiguous()
+        act = torch.as_tensor(actions, dtype=torch.float32, device=ctx.torch_device).reshape(len(states), -1).contiguous()
+        packed, xpos, xquat, ctrl = ctx.env_step_batch(packed, act)
+        return [State(self, packed[b], xpos[b], xquat[b], ctrl[b]) for b in range(len(states))]
+
     def pipeline_init(self, q, qd):
         from dial_mpc_amd.envs.state import State
         return State.from_reset(self, self._context(), q, qd).pipeline_state

@@ -15,6 +15,7 @@
  *   dial_rollout        <- MBDPI.rollout_us_vmap      dial_mpc/core/dial_core.py:36-42,80-81
  *   dial_reverse_once   <- MBDPI.reverse_once         dial_mpc/core/dial_core.py:103-145
  *   dial_shift          <- MBDPI.shift                dial_mpc/core/dial_core.py:160-166
+ *   dial_reverse_once_batch  <- jax.vmap(MBDPI.reverse_once) over (state, rng, Ybar, noise_scale): M plans, one launch
  *   dial_env_step       <- BaseEnv/<Env>.step         dial_mpc/envs/unitree_go2_env.py:126-261,
  *                                                     :403-521, dial_mpc/envs/unitree_h1_env.py:181-321,
  *                                                     :696-858 (H1 loco), dial_mpc/envs/manipulation.py:63-115
@@ -60,6 +61,7 @@ extern "C" {
 #define DIAL_MAX_NODE 10   /* Hnode+1                                            */
 #define DIAL_INFO_N 48     /* floats of env info in the packed state             */
 #define DIAL_MAX_CMD 16    /* randomize_tasks: velocity commands of the episodes step / 500 = 0, 1, ... (wraps)  */
+#define DIAL_MAX_PLANS 1024 /* dial_options.plan_cap: plans of one grouped launch (dial_reverse_once_batch)    */
 
 /* joint types (MuJoCo numbering) */
 #define DIAL_JNT_FREE 0
@@ -355,6 +357,9 @@ typedef struct dial_options {
                                  other side of 2304 (N = 4096 over 2 or 4 ranks) equals the fused run at rounding level, not bit for
                                  bit; ranks of one run always agree with each other (same shard size).  pair_mode 1 or 2 on every
                                  context restores bit-equality across shardings.                                                  */
+  int32_t plan_cap;           /* plans one dial_reverse_once_batch[_rng] call may carry, 0 .. DIAL_MAX_PLANS (0 = 1): the rollout scratch,
+                                 the weights and K4b's partial sums are sized for plan_cap x (Nsample + 1) rollouts.  0 / 1 allocate exactly
+                                 what a context without grouped plans needs.                                                       */
 } dial_options;
 
 /* host pointers; copies model/task/cfg to the device and allocates scratch for
@@ -451,13 +456,38 @@ int dial_shard_ybar_gathered_rng(dial_ctx* ctx, const float* gathered, int world
 int dial_shard_reduce_gathered(dial_ctx* ctx, const float* gathered, int world, int per, int n_total, int n_begin,
                                int n_local, int with_mean, float* rews_all_out, float* packed_out, void* stream);
 
+/* Grouped planning: M independent reverse_once iterations of ONE context (same model, task, cfg and kernel instantiation) from M
+ * states in one rollout launch -- what jax.vmap(MBDPI.reverse_once) over (state, rng, Ybar, noise_scale) computes.
+ *   states:[M,nstate]  Ybar_in:[M,Hnode+1,nu]  noise_scale:[M,ns] (ns = Hnode+1 or 1, the same for every plan)
+ *   eps:[M,Nsample,Hnode+1,nu]  ->  Ybar_out:[M,Hnode+1,nu]  rews:[M,Nsample+1] (last of each row = that plan's mean trajectory)
+ *   qbar:[M,T,nq]  qdbar:[M,T,nv]  xbar:[M,T,(nbody-1)*3]  (all three NULL: the lean iteration, mean action only, as dial_reverse_once)
+ * Plan g, sample n is batch rollout g (Nsample + 1) + n; row g (Nsample + 1) + Nsample is plan g's mean trajectory (also the row of
+ * dial_set_state_trace).  Each plan's softmax is its own: a degenerate plan (std = 0 -> NaN, see dial_reverse_once) leaves the
+ * others untouched.  Noise key of the _rng form: plan g, sample n draws the noise of GLOBAL sample g Nsample + n, i.e. plan g's
+ * noise is rows [g Nsample, (g + 1) Nsample) of dial_rng_fill(seed, counter, 0, M Nsample); plan 0 equals dial_reverse_once_rng.
+ * M = 1 runs exactly dial_reverse_once[_rng].  M > 1 launches every rollout alike (plain grid, rollout queue, Go2 pair kernel, Allegro
+ * time-sliced queue; no mean-trajectory relay / interleaving / split launch).  Fails with DIAL_ERR_ARG (dial_last_error names the
+ * reason) when M is outside 1 .. options.plan_cap, the context is sharded (n_local_cap < Nsample) or ns is not 1 / Hnode+1. */
+int dial_reverse_once_batch(dial_ctx* ctx, const float* states, const float* Ybar_in, const float* noise_scale, int ns,
+                            const float* eps, int M, float* Ybar_out, float* rews, float* qbar, float* qdbar, float* xbar,
+                            void* stream);
+int dial_reverse_once_batch_rng(dial_ctx* ctx, const float* states, const float* Ybar_in, const float* noise_scale, int ns,
+                                uint64_t seed, uint32_t counter, int M, float* Ybar_out, float* rews, float* qbar, float* qdbar,
+                                float* xbar, void* stream);
+
 /* K5. MBDPI.shift (dial_core.py:160-166): Y:[Hnode+1,nu] in place. */
 int dial_shift(dial_ctx* ctx, float* Y, void* stream);
+/* The same for M plans in one launch (one workgroup each): Y:[M,Hnode+1,nu] in place. */
+int dial_shift_batch(dial_ctx* ctx, float* Y, int M, void* stream);
 
 /* K6. env.step on the true state (B = 1), state updated in place; xpos_out:[(nbody-1)*3],
  * xquat_out:[(nbody-1)*4], ctrl_out:[nu] optional (may be NULL).                    */
 int dial_env_step(dial_ctx* ctx, float* state, const float* action, float* xpos_out,
                   float* xquat_out, float* ctrl_out, void* stream);
+/* The same for M states in ONE launch (one workgroup each): states:[M,nstate] in place, actions:[M,nu],
+ * xpos_out:[M,(nbody-1)*3] / xquat_out:[M,(nbody-1)*4] / ctrl_out:[M,nu] optional.                           */
+int dial_env_step_batch(dial_ctx* ctx, float* states, const float* actions, float* xpos_out,
+                        float* xquat_out, float* ctrl_out, int M, void* stream);
 
 /* env.reset: state <- (qpos, qvel, zeros) followed by mjx.forward (pipeline_init), info
  * initialised for the task.  qpos:[nq], qvel:[nv] device pointers.                  */
