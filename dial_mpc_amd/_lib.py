@@ -169,6 +169,12 @@ def load(path: Optional[str] = None):
     except AttributeError:
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack the grouped entry points)
             raise
+    try:
+        lib.dial_create_plugin.argtypes = [ctypes.POINTER(vp), vp, vp, vp, ci, vp, ctypes.c_char_p, vp, ci]
+        lib.dial_set_user_params.argtypes = [vp, vp, ci]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack the task-plugin entry points)
+            raise
     lib.dial_env_reset.argtypes = [vp, fp, fp, fp, fp, fp, vp]
     lib.dial_env_reset_batch.argtypes = [vp, fp, fp, fp, fp, fp, ci, vp]
     lib.dial_status.argtypes = [vp]
@@ -189,7 +195,8 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
             "dial_shard_rollout_rng", "dial_rng_fill", "dial_shard_ybar_rng", "dial_shard_pack_rewards",
             "dial_shard_ybar_gathered", "dial_shard_ybar_gathered_rng", "dial_shard_reduce_gathered", "dial_shift", "dial_env_step", "dial_env_reset", "dial_env_reset_batch",
             "dial_status", "dial_set_timing", "dial_get_rollout_ms", "dial_abi_sizes",
-            "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch")
+            "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch",
+            "dial_create_plugin", "dial_set_user_params")
 
 
 def _ptr(t) -> Optional[int]:
@@ -209,11 +216,13 @@ class Context:
 
     def __init__(self, model: "_abi.DialModel", task: "_abi.DialTask", cfg: Optional["_abi.DialCfg"],
                  device: Optional[int] = None, n_local_cap: Optional[int] = None, lib_path: Optional[str] = None,
-                 options: Optional[dict] = None):
+                 options: Optional[dict] = None, plugin: Optional[str] = None, user_params=None):
         """n_local_cap: size the rollout scratch for that many local samples (one rank of a sharded run).
         lib_path: another build of the library (measurement variants, e.g. libdialhip_ieee.so).
         options: fields of `dial_options` (include/dial_mpc.h) -- launch-shape / measurement switches, e.g.
-        dict(no_queue=1); none of them changes a result bit.  The library itself reads no environment variables."""
+        dict(no_queue=1); none of them changes a result bit.  The library itself reads no environment variables.
+        plugin: path of a task plugin (dial_mpc_amd/plugin.py: build_plugin) whose kernels serve this context (task.kind =
+        DIAL_TASK_USER; dial_create_plugin), user_params its float task parameters (<= DIAL_USER_PARAMS; set_user_params)."""
         import torch
         self.lib = load(lib_path)
         if not torch.cuda.is_available():
@@ -231,12 +240,40 @@ class Context:
         if unknown:
             raise ValueError(f"unknown dial_options fields: {sorted(unknown)}")
         opts = _abi.fill(_abi.DialOptions(), self.options)
+        self.plugin = plugin
+        if plugin is not None:
+            if n_local_cap is not None:
+                raise DialHipError("task-plugin contexts cannot be sharded (n_local_cap)")
+            vals = [] if user_params is None else list(user_params)
+            p = self._params(vals)
+            rc = self.lib.dial_create_plugin(ctypes.byref(h), ctypes.addressof(model), ctypes.addressof(task),
+                                             ctypes.addressof(cfg) if cfg is not None else None, self.device, ctypes.addressof(opts),
+                                             os.fsencode(plugin), ctypes.addressof(p), len(vals))
+            if rc != 0:
+                raise DialHipError(f"dial_create_plugin failed ({rc}): {self.lib.dial_last_error(None).decode()}")
+            self.h = h
+            return
         rc = self.lib.dial_create_ex(ctypes.byref(h), ctypes.addressof(model), ctypes.addressof(task),
                                      ctypes.addressof(cfg) if cfg is not None else None, self.device,
                                      -1 if (n_local_cap is None or cfg is None) else int(n_local_cap), ctypes.addressof(opts))
         if rc != 0:
             raise DialHipError(f"dial_create failed ({rc}): {self.lib.dial_last_error(None).decode()}")
         self.h = h
+
+    @staticmethod
+    def _params(values):
+        v = [] if values is None else [float(x) for x in values]
+        cap = _abi.MACROS["DIAL_USER_PARAMS"]
+        if len(v) > cap:
+            raise ValueError(f"{len(v)} user parameters; a task plugin takes at most DIAL_USER_PARAMS = {cap}")
+        return (ctypes.c_float * max(1, len(v)))(*v) if v else (ctypes.c_float * 1)()
+
+    def set_user_params(self, values):
+        """New float task parameters of a task-plugin context (no rebuild; synchronises the device)."""
+        vals = [] if values is None else list(values)
+        p = self._params(vals)
+        n = len(vals)
+        self._check(self.lib.dial_set_user_params(self.h, ctypes.addressof(p), n), "dial_set_user_params")
 
     def __del__(self):
         try:

@@ -79,8 +79,9 @@ class MBDPI:
         if self.n_plans > 1:
             options = dict(options or {}, plan_cap=self.n_plans)
         # a rank's rollout scratch is sized by its own shard, not by the global sample count
+        extra = env.context_kwargs() if hasattr(env, "context_kwargs") else {}   # (custom envs: their task plugin, envs/custom_env.py)
         self.ctx = _lib.Context(env.make_model(), env.make_task(), self.cfg, device,
-                                n_local_cap=None if self.world == 1 else self._per, options=options)
+                                n_local_cap=None if self.world == 1 else self._per, options=options, **extra)
         if hasattr(env, "bind_device"):
             env.bind_device(self.ctx.device)
         dev = self.ctx.torch_device

@@ -154,6 +154,8 @@ struct Dims {
 #else
   static constexpr bool pre_ctrl = quad_stage;
 #endif
+  // a user reward (DIAL_TASK_USER, csrc/user_reward.h) instead of the built-in ones: the instantiations of a task plugin only (DimsUser)
+  static constexpr bool user = false;
 };
 using DimsGo2 = Dims<true, 19, 18, 12, 14, 13, 5, 5, 4, 12, TopoGo2, true, 192>;
 using DimsH1 = Dims<true, 26, 25, 19, 21, 20, 3, 3, 4, 19, TopoH1, true, 256>;
@@ -165,6 +167,12 @@ using DimsGo2Crate = Dims<true, 19, 18, 12, 15, 13, 17, 5, 52, 12, TopoGo2, fals
 using DimsH1PushCrate = Dims<true, 27, 26, 19, 22, 21, 9, 3, 28, 19, TopoH1PushCrate, false, 2, false, 0, 4, true, 1, true>;
 using DimsMax = Dims<false, DIAL_MAX_Q, DIAL_MAX_V, DIAL_MAX_U, DIAL_MAX_BODY, DIAL_MAX_JNT, DIAL_MAX_GEOM,
                      DIAL_MAX_SITE, DIAL_MAX_CON, DIAL_MAX_LIM>;
+// A task plugin's instantiation (dial_mpc_amd/plugin.py): the generic feature set at the model's compile-time dimensions, dense
+// dof order, constants staged in LDS, and the user reward in place of the built-in ones (rollout_body.h: env_step)
+template <int NQ_, int NV_, int NU_, int NB_, int NJ_, int NG_, int NS_, int NC_, int NL_, int NFRI_>
+struct DimsUser : Dims<true, NQ_, NV_, NU_, NB_, NJ_, NG_, NS_, NC_, NL_, TopoDense, false, 2, false, 0, 4, true, NFRI_, true> {
+  static constexpr bool user = true;
+};
 
 // compile-time loop: f(std::integral_constant<int, I>) for I in [B, E)
 #include <type_traits>
@@ -202,9 +210,17 @@ struct CModelGeneric<D, true> {
   float pc_wanted_zmax;
 };
 
+// What only a task plugin's instantiation carries: the user reward's parameters (dial_set_user_params).  An EMPTY base elsewhere.
+template <class D, bool USER = D::user>
+struct CModelUser {};
+template <class D>
+struct CModelUser<D, true> {
+  float user_params[DIAL_USER_PARAMS];
+};
+
 // Everything one env.step reads that is constant across samples and steps.
 template <class D_>
-struct CModel : CModelGeneric<D_> {
+struct CModel : CModelGeneric<D_>, CModelUser<D_> {
   using D = D_;
   // ---- scalars
   int32_t nq, nv, nu, nbody, njnt, ngeom, nsite, ncon, nlim, nefc;

@@ -12,6 +12,7 @@
 //   wsum_*_kernel    K4b: weighted means of Y0s / q / qd / x.pos, two deterministic passes (plan on grid.z).
 //   shift_kernel     K5, env_step_kernel / env_reset_kernel  K6 (one workgroup per state / plan).
 // There is no CPU fallback: every entry point needs a HIP device and fails with DIAL_ERR_HIP otherwise.
+#include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -21,6 +22,7 @@
 #include <vector>
 
 #include "kernel_list.h"
+#include "plugin_ops.h"
 
 // the kernels are compiled in their own translation units, one per robot family (kern_family.hip, built in parallel)
 #define DIAL_X(D, WPB, OCC, Q, TR) \
@@ -338,7 +340,10 @@ struct dial_ctx {
   dial_cfg hc;
   dial_derived hd;
   bool has_cfg = false;
-  int inst = 0;               // 0 generic (DimsMax), 1 Go2, 2 H1, 3 H1 loco, 4 Allegro (elliptic cones), 5 Go2 crate climb, 6 H1 push crate
+  int inst = 0;               // 0 generic (DimsMax), 1 Go2, 2 H1, 3 H1 loco, 4 Allegro (elliptic cones), 5 Go2 crate climb, 6 H1 push crate,
+                              // 7 a task plugin's instantiation (dial_create_plugin: `plug`)
+  const dial_plugin_ops* plug = nullptr;   // inst 7: the plugin's host functions (the library stays loaded for the process)
+  std::vector<char> plug_cm;               // inst 7: host copy of the constants (dial_set_user_params rewrites the parameters)
   void* dcm = nullptr;        // CModel<D> of the chosen instantiation (device)
   dial_task* dtask = nullptr;
   dial_cfg* dcfg = nullptr;
@@ -440,8 +445,51 @@ int dial_create_sharded(dial_ctx** out, const dial_model* model, const dial_task
   return dial_create_ex(out, model, task, cfg, device, n_local_cap, nullptr);
 }
 
+static int create_impl(dial_ctx** out, const dial_model* model, const dial_task* task, const dial_cfg* cfg, int device,
+                       int n_local_cap, const dial_options* opts, const dial_plugin_ops* plug, const float* params, int n_params);
+
 int dial_create_ex(dial_ctx** out, const dial_model* model, const dial_task* task, const dial_cfg* cfg, int device,
                    int n_local_cap, const dial_options* opts) {
+  return create_impl(out, model, task, cfg, device, n_local_cap, opts, nullptr, nullptr, 0);
+}
+
+int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task* task, const dial_cfg* cfg, int device,
+                       const dial_options* opts, const char* plugin_path, const float* params, int n_params) {
+  if (!out || !model || !task || !plugin_path) return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: null argument");
+  if (task->kind != DIAL_TASK_USER) return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: task.kind must be DIAL_TASK_USER");
+  if (n_params < 0 || n_params > DIAL_USER_PARAMS || (n_params > 0 && !params))
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: n_params must be in 0 .. DIAL_USER_PARAMS");
+  // (never dlclose'd: the HIP runtime holds the plugin's code object for the life of the process)
+  void* h = dlopen(plugin_path, RTLD_NOW | RTLD_LOCAL);
+  if (!h) return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: dlopen failed: ") + dlerror());
+  dial_plugin_entry entry = (dial_plugin_entry)dlsym(h, DIAL_PLUGIN_SYMBOL);
+  if (!entry) return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + plugin_path + " does not export " DIAL_PLUGIN_SYMBOL);
+  const dial_plugin_ops* ops = entry();
+  if (!ops || ops->abi_version != DIAL_PLUGIN_ABI_VERSION || ops->sizeof_model != sizeof(dial_model) || ops->sizeof_task != sizeof(dial_task) ||
+      ops->sizeof_cfg != sizeof(dial_cfg) || ops->sizeof_derived != sizeof(dial_derived) || ops->sizeof_io != sizeof(dial::RolloutIO))
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin was built against another version of the library (ABI mismatch; rebuild it)");
+  if (model->cone != DIAL_CONE_PYRAMIDAL)
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: task plugins support pyramidal friction cones only (the model's cone is elliptic)");
+  if (kbi_unique_rows(model) > DIAL_KBI_ROWS)
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the model has more distinct (solref, solimp) rows than the impedance table holds (DIAL_KBI_ROWS)");
+  const int md[10] = {model->nq, model->nv, model->nu, model->nbody, model->njnt, model->ngeom, model->nsite, model->ncon, model->nlim, model->nfri};
+  for (int k = 0; k < 10; k++)
+    if (md[k] != ops->dims[k]) return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the model's dimensions differ from the plugin's (rebuild the plugin for this model)");
+  return create_impl(out, model, task, cfg, device, -1, opts, ops, params, n_params);
+}
+
+int dial_set_user_params(dial_ctx* ctx, const float* params, int n) {
+  if (!ctx || n < 0 || n > DIAL_USER_PARAMS || (n > 0 && !params)) return fail(ctx, DIAL_ERR_ARG, "dial_set_user_params: bad argument (n must be in 0 .. DIAL_USER_PARAMS)");
+  if (!ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_set_user_params: the context has no task plugin (dial_create_plugin)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->plug->set_params(ctx->plug_cm.data(), params, n);
+  HIP_TRY(ctx, hipDeviceSynchronize());   // (launches in flight read the constants)
+  HIP_TRY(ctx, hipMemcpy(ctx->dcm, ctx->plug_cm.data(), ctx->plug->cmodel_bytes, hipMemcpyHostToDevice));
+  return DIAL_OK;
+}
+
+static int create_impl(dial_ctx** out, const dial_model* model, const dial_task* task, const dial_cfg* cfg, int device,
+                       int n_local_cap, const dial_options* opts, const dial_plugin_ops* plug, const float* params, int n_params) {
   if (!out || !model || !task) return fail(nullptr, DIAL_ERR_ARG, "dial_create: null argument");
   if (n_local_cap < 0) n_local_cap = cfg ? cfg->Nsample : 0;
   if (cfg && n_local_cap > cfg->Nsample) return fail(nullptr, DIAL_ERR_ARG, "dial_create_ex: n_local_cap must be in [0, Nsample]");
@@ -456,7 +504,9 @@ int dial_create_ex(dial_ctx** out, const dial_model* model, const dial_task* tas
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(nullptr, DIAL_ERR_HIP, "dial_create: no HIP device available (the HIP path has no CPU fallback)");
   if (device < 0 || device >= ndev) return fail(nullptr, DIAL_ERR_ARG, "dial_create: bad device index");
-  if (task->kind < DIAL_TASK_GO2_WALK || task->kind > DIAL_TASK_H1_PUSH_CRATE)
+  if (task->kind == DIAL_TASK_USER && !plug)
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create: DIAL_TASK_USER needs a task plugin that holds the reward (dial_create_plugin)");
+  if ((task->kind < DIAL_TASK_GO2_WALK || task->kind > DIAL_TASK_H1_PUSH_CRATE) && !(plug && task->kind == DIAL_TASK_USER))
     return fail(nullptr, DIAL_ERR_UNSUPPORTED, "dial_create: unknown task kind");
   {   // the reward phase unrolls over the feet of the task's robot (rollout_body.h: reward_phase)
     const bool go2 = task->kind == DIAL_TASK_GO2_WALK || task->kind == DIAL_TASK_GO2_SEQ_JUMP || task->kind == DIAL_TASK_GO2_CRATE;
@@ -509,6 +559,7 @@ int dial_create_ex(dial_ctx** out, const dial_model* model, const dial_task* tas
   ctx->plan_cap = opt.plan_cap > 1 ? opt.plan_cap : 1;
   ctx->hm = *model;
   ctx->ht = *task;
+  ctx->plug = plug;
   int rc = dial_build_derived(model, &ctx->hd);
   if (rc != DIAL_OK) { delete ctx; return fail(nullptr, rc, "dial_create: unsupported model topology"); }
   ctx->nx = (model->nbody - 1) * 3;
@@ -593,7 +644,24 @@ int dial_create_ex(dial_ctx** out, const dial_model* model, const dial_task* tas
     const bool kbi_ok = kbi_unique_rows(model) <= DIAL_KBI_ROWS;
     const bool own = !opt.force_generic && kbi_ok;
     // (Dims::pre_ctrl instantiations run ONE physics step per control step -- every shipped Go2 task; another ratio: the capacity-dimension kernel)
-    if (own && dims_match<DimsGo2>(model) && derived_fits<DimsGo2>(&ctx->hd) && kind_ok(dial::task_kind_mask<DimsGo2>()) &&
+    if (plug) {   // a task plugin: its own instantiation, whatever the options say about the built-in ones
+      ctx->inst = 7; ctx->wpb = plug->wpb;
+      if (const char* why = plug->check(model, &ctx->hd)) { dial_destroy(ctx); return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + why); }
+      dial_plugin_layout lay;
+      plug->layout(model, cfg, opt.con_cap, &lay);
+      ctx->cm_bytes = lay.cm_bytes;
+      ctx->con_cap = lay.con_cap;
+      ctx->ovf_words = lay.ovf_words;
+      ctx->ws_words = lay.ws_words;
+      ctx->lds_bytes = ctx->cm_bytes + (size_t)lay.ws0_words * sizeof(float);
+      ctx->lds_rollout = ctx->cm_bytes + (size_t)ctx->wpb * ctx->ws_words * sizeof(float);
+      ctx->plug_cm.assign(plug->cmodel_bytes, 0);
+      plug->fill(ctx->plug_cm.data(), model, task, &ctx->hd, params, n_params);
+      hipError_t e = hipMalloc(&ctx->dcm, (plug->cmodel_bytes + 15) / 16 * 16);
+      if (e == hipSuccess) e = hipMemcpy(ctx->dcm, ctx->plug_cm.data(), plug->cmodel_bytes, hipMemcpyHostToDevice);
+      urc = e == hipSuccess ? DIAL_OK : DIAL_ERR_HIP;
+    }
+    else if (own && dims_match<DimsGo2>(model) && derived_fits<DimsGo2>(&ctx->hd) && kind_ok(dial::task_kind_mask<DimsGo2>()) &&
         (!DimsGo2::pre_ctrl || task->n_frames == 1)) { ctx->inst = 1; ctx->wpb = 1; urc = upload(DimsGo2{}); }
     else if (own && dims_match<DimsH1>(model) && derived_fits<DimsH1>(&ctx->hd) && kind_ok(dial::task_kind_mask<DimsH1>())) { ctx->inst = 2; ctx->wpb = 3; urc = upload(DimsH1{}); }
     else if (own && dims_match<DimsH1Loco>(model) && derived_fits<DimsH1Loco>(&ctx->hd) && kind_ok(dial::task_kind_mask<DimsH1Loco>())) { ctx->inst = 3; ctx->wpb = 2; urc = upload(DimsH1Loco{}); }
@@ -630,6 +698,7 @@ int dial_create_ex(dial_ctx** out, const dial_model* model, const dial_task* tas
       if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rollout_kernel<D, DIAL_CRATE_WPB, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_rollout); \
       if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rollout_kernel<D, DIAL_CRATE_WPB, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_rollout); \
     }
+    if (ctx->inst == 7) e = ctx->plug->set_lds(ctx->lds_rollout);
     if (ctx->inst == 5) { DIAL_BIG_LDS(DimsGo2Crate) }
     if (ctx->inst == 6) { DIAL_BIG_LDS(DimsH1PushCrate) }
 #undef DIAL_BIG_LDS
@@ -661,6 +730,7 @@ int dial_create_ex(dial_ctx** out, const dial_model* model, const dial_task* tas
     else if (ctx->inst == 4) DIAL_RESIDENT(DimsAllegro, DIAL_ALLEGRO_WPB);
     else if (ctx->inst == 5) DIAL_RESIDENT(DimsGo2Crate, DIAL_CRATE_WPB);
     else if (ctx->inst == 6) DIAL_RESIDENT(DimsH1PushCrate, DIAL_CRATE_WPB);
+    else if (ctx->inst == 7) e = ctx->plug->occupancy(&nb, ctx->lds_rollout);
     else DIAL_RESIDENT(DimsMax, 1);
 #undef DIAL_RESIDENT
     ctx->n_simd = 4 * prop.multiProcessorCount;
@@ -988,6 +1058,7 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
     else if (ctx->inst == 4) DIAL_LAUNCH_TRACE(DimsAllegro, DIAL_ALLEGRO_WPB);
     else if (ctx->inst == 5) DIAL_LAUNCH_TRACE(DimsGo2Crate, DIAL_CRATE_WPB);
     else if (ctx->inst == 6) DIAL_LAUNCH_TRACE(DimsH1PushCrate, DIAL_CRATE_WPB);
+    else if (ctx->inst == 7) HIP_TRY(ctx, ctx->plug->rollout(2, blocks, ctx->lds_rollout, st, ctx->dcm, ctx->dtask, ctx->dcfg, &io, B, ctx->ws_words, nullptr));
     else DIAL_LAUNCH_TRACE(DimsMax, 1);
   } else
   if (large)
@@ -1000,6 +1071,7 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
   else if (ctx->inst == 4) DIAL_LAUNCH_ROLLOUT(DimsAllegro, DIAL_ALLEGRO_WPB);
   else if (ctx->inst == 5) DIAL_LAUNCH_ROLLOUT(DimsGo2Crate, DIAL_CRATE_WPB);
   else if (ctx->inst == 6) DIAL_LAUNCH_ROLLOUT(DimsH1PushCrate, DIAL_CRATE_WPB);
+  else if (ctx->inst == 7) HIP_TRY(ctx, ctx->plug->rollout(next ? 1 : 0, blocks, ctx->lds_rollout, st, ctx->dcm, ctx->dtask, ctx->dcfg, &io, B, ctx->ws_words, next));
   else DIAL_LAUNCH_ROLLOUT(DimsMax, 1);
 #undef DIAL_LAUNCH_ROLLOUT
 #undef DIAL_LAUNCH_ROLLOUT_Q
@@ -1043,6 +1115,7 @@ static int shard_rollout_impl(dial_ctx* ctx, const float* state, const float* Yb
 
 int dial_shard_rollout(dial_ctx* ctx, const float* state, const float* Ybar_in, const float* noise_scale, int ns,
                        const float* eps, int n_local, int with_mean, float* rews_local, void* stream) {
+  if (ctx && ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_shard_rollout: sharded use of a task-plugin context is not supported");
   return shard_rollout_impl(ctx, state, Ybar_in, noise_scale, ns, eps, 0, 0, 0, 0, n_local, with_mean, rews_local,
                             stream, "dial_shard_rollout");
 }
@@ -1050,6 +1123,7 @@ int dial_shard_rollout(dial_ctx* ctx, const float* state, const float* Ybar_in, 
 int dial_shard_rollout_rng(dial_ctx* ctx, const float* state, const float* Ybar_in, const float* noise_scale, int ns,
                            uint64_t seed, uint32_t counter, int n_begin, int n_local, int with_mean,
                            float* rews_local, void* stream) {
+  if (ctx && ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_shard_rollout_rng: sharded use of a task-plugin context is not supported");
   return shard_rollout_impl(ctx, state, Ybar_in, noise_scale, ns, nullptr, 1, seed, counter, n_begin, n_local,
                             with_mean, rews_local, stream, "dial_shard_rollout_rng");
 }
@@ -1115,10 +1189,12 @@ static int shard_reduce_impl(dial_ctx* ctx, const float* rews_all, const float* 
 }
 int dial_shard_reduce(dial_ctx* ctx, const float* rews_all, int n_total, int n_begin, int n_local, int with_mean,
                       float* packed_out, void* stream) {
+  if (ctx && ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_shard_reduce: sharded use of a task-plugin context is not supported");
   return shard_reduce_impl(ctx, rews_all, nullptr, 0, 0, nullptr, n_total, n_begin, n_local, with_mean, packed_out, stream, "dial_shard_reduce");
 }
 int dial_shard_reduce_gathered(dial_ctx* ctx, const float* gathered, int world, int per, int n_total, int n_begin, int n_local,
                                int with_mean, float* rews_all_out, float* packed_out, void* stream) {
+  if (ctx && ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_shard_reduce_gathered: sharded use of a task-plugin context is not supported");
   return shard_reduce_impl(ctx, nullptr, gathered, world, per, rews_all_out, n_total, n_begin, n_local, with_mean, packed_out, stream,
                            "dial_shard_reduce_gathered");
 }
@@ -1149,29 +1225,34 @@ static int shard_ybar_impl(dial_ctx* ctx, const float* rews_all, const float* ga
 
 int dial_shard_ybar(dial_ctx* ctx, const float* rews_all, int n_total, const float* eps_all, const float* Ybar_in,
                     const float* noise_scale, int ns, float* Ybar_out, void* stream) {
+  if (ctx && ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_shard_ybar: sharded use of a task-plugin context is not supported");
   return shard_ybar_impl(ctx, rews_all, nullptr, 0, 0, nullptr, n_total, eps_all, 0, 0, 0, Ybar_in, noise_scale, ns, Ybar_out, stream, "dial_shard_ybar");
 }
 
 int dial_shard_ybar_rng(dial_ctx* ctx, const float* rews_all, int n_total, uint64_t seed, uint32_t counter,
                         const float* Ybar_in, const float* noise_scale, int ns, float* Ybar_out, void* stream) {
+  if (ctx && ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_shard_ybar_rng: sharded use of a task-plugin context is not supported");
   return shard_ybar_impl(ctx, rews_all, nullptr, 0, 0, nullptr, n_total, nullptr, 1, seed, counter, Ybar_in, noise_scale, ns, Ybar_out, stream,
                          "dial_shard_ybar_rng");
 }
 
 int dial_shard_ybar_gathered(dial_ctx* ctx, const float* gathered, int world, int per, int n_total, const float* eps_all,
                              const float* Ybar_in, const float* noise_scale, int ns, float* rews_all_out, float* Ybar_out, void* stream) {
+  if (ctx && ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_shard_ybar_gathered: sharded use of a task-plugin context is not supported");
   return shard_ybar_impl(ctx, nullptr, gathered, world, per, rews_all_out, n_total, eps_all, 0, 0, 0, Ybar_in, noise_scale, ns, Ybar_out, stream,
                          "dial_shard_ybar_gathered");
 }
 
 int dial_shard_ybar_gathered_rng(dial_ctx* ctx, const float* gathered, int world, int per, int n_total, uint64_t seed, uint32_t counter,
                                  const float* Ybar_in, const float* noise_scale, int ns, float* rews_all_out, float* Ybar_out, void* stream) {
+  if (ctx && ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_shard_ybar_gathered_rng: sharded use of a task-plugin context is not supported");
   return shard_ybar_impl(ctx, nullptr, gathered, world, per, rews_all_out, n_total, nullptr, 1, seed, counter, Ybar_in, noise_scale, ns, Ybar_out,
                          stream, "dial_shard_ybar_gathered_rng");
 }
 
 int dial_shard_pack_rewards(dial_ctx* ctx, const float* gathered, int world, int per, int n_total, float* rews_all,
                             void* stream) {
+  if (ctx && ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_shard_pack_rewards: sharded use of a task-plugin context is not supported");
   if (!ctx || !gathered || !rews_all || world < 1 || per < 1 || n_total < 1 || (long long)world * per < n_total)
     return fail(ctx, DIAL_ERR_ARG, "dial_shard_pack_rewards: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1288,6 +1369,7 @@ static int env_step_launch(dial_ctx* ctx, float* state, const float* action, flo
   else if (ctx->inst == 4) DIAL_LAUNCH_STEP(DimsAllegro);
   else if (ctx->inst == 5) DIAL_LAUNCH_STEP(DimsGo2Crate);
   else if (ctx->inst == 6) DIAL_LAUNCH_STEP(DimsH1PushCrate);
+  else if (ctx->inst == 7) HIP_TRY(ctx, ctx->plug->env_step(n, ctx->lds_bytes, (hipStream_t)stream, ctx->dcm, ctx->dtask, state, action, xpos_out, xquat_out, ctrl_out));
   else DIAL_LAUNCH_STEP(DimsMax);
 #undef DIAL_LAUNCH_STEP
   HIP_TRY(ctx, hipGetLastError());
@@ -1315,6 +1397,7 @@ static int env_reset_launch(dial_ctx* ctx, const float* qpos, const float* qvel,
   else if (ctx->inst == 4) DIAL_LAUNCH_RESET(DimsAllegro);
   else if (ctx->inst == 5) DIAL_LAUNCH_RESET(DimsGo2Crate);
   else if (ctx->inst == 6) DIAL_LAUNCH_RESET(DimsH1PushCrate);
+  else if (ctx->inst == 7) HIP_TRY(ctx, ctx->plug->env_reset(n, ctx->lds_bytes, (hipStream_t)stream, ctx->dcm, qpos, qvel, state, xpos_out, xquat_out));
   else DIAL_LAUNCH_RESET(DimsMax);
 #undef DIAL_LAUNCH_RESET
   HIP_TRY(ctx, hipGetLastError());

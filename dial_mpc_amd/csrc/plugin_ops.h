@@ -1,0 +1,141 @@
+// plugin_ops.h -- the host side of ONE kernel instantiation as a table of functions: what a task plugin (plugin.hip, built by
+// dial_mpc_amd/plugin.py for one model and one user reward) exports and libdialhip.so calls for a context of dial_create_plugin.
+// The table carries the per-instantiation work of dial_create and of the launches -- sizing and filling the constants, the
+// dynamic-LDS opt-in, the occupancy query, the rollout / env.step / env.reset launches -- so that the library keeps everything
+// else (the queue / relay decisions of launch_rollout, K4 / K5, the sharded and grouped entry points) for plugin contexts too.
+// The plugin is built from the same csrc sources as the library (its cache key hashes them), and the table records the sizes of
+// the structs that cross the boundary; dial_create_plugin refuses a plugin whose ABI version or sizes differ.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include <new>
+
+#include "rollout_kernel.h"
+
+#define DIAL_PLUGIN_ABI_VERSION 1
+#define DIAL_PLUGIN_SYMBOL "dial_plugin_ops_v1"
+
+// what dial_create's `upload` computes for an instantiation: LDS layout and the generic feature set's contact cap
+struct dial_plugin_layout {
+  int cm_bytes;      // constants staged in LDS (16-byte multiple)
+  int ws_words;      // one rollout's workspace (wavefront)
+  int ws0_words;     // env.step / env.reset workspace (no node array)
+  int con_cap;       // touching-contact cap of the capped workspace (0: no cap)
+  int ovf_words;     // words of one overflow area (con_cap > 0)
+};
+
+struct dial_plugin_ops {
+  int abi_version;                 // DIAL_PLUGIN_ABI_VERSION
+  int dims[10];                    // nq nv nu nbody njnt ngeom nsite ncon nlim nfri of the instantiation
+  int wpb;                         // wavefronts per workgroup of its rollout kernel
+  size_t cmodel_bytes;             // sizeof(CModel<D>)
+  size_t sizeof_model, sizeof_task, sizeof_cfg, sizeof_derived, sizeof_io;   // (ABI check)
+  // does the model fit the instantiation exactly (dimensions, impedance table, pyramidal cones)?  0 = yes, else a reason
+  const char* (*check)(const dial_model* m, const dial_derived* dv);
+  int (*layout)(const dial_model* m, const dial_cfg* cfg, int opt_con_cap, dial_plugin_layout* out);
+  // the constants (host copy, cmodel_bytes) with the user parameters params[0 .. n) (the rest zero)
+  void (*fill)(void* host_cm, const dial_model* m, const dial_task* t, const dial_derived* dv, const float* params, int n);
+  void (*set_params)(void* host_cm, const float* params, int n);
+  hipError_t (*set_lds)(size_t lds_rollout);   // dynamic-LDS opt-in of the rollout kernels (> 64 KiB)
+  hipError_t (*occupancy)(int* blocks_per_cu, size_t lds_rollout);
+  // variant 0 plain grid, 1 rollout queue (next != nullptr), 2 state trace
+  hipError_t (*rollout)(int variant, int blocks, size_t lds, hipStream_t st, const void* dcm, const dial_task* dtask, const dial_cfg* dcfg,
+                        const dial::RolloutIO* io, int B, int ws_words, int* next);
+  hipError_t (*env_step)(int n, size_t lds, hipStream_t st, const void* dcm, const dial_task* dtask, float* state, const float* action,
+                         float* xpos_out, float* xquat_out, float* ctrl_out);
+  hipError_t (*env_reset)(int n, size_t lds, hipStream_t st, const void* dcm, const float* qpos, const float* qvel, float* state,
+                          float* xpos_out, float* xquat_out);
+};
+
+typedef const dial_plugin_ops* (*dial_plugin_entry)(void);
+
+// ---- the table of one instantiation D (rollout kernels with WPB wavefronts per workgroup, occupancy target 3)
+template <class D, int WPB>
+struct PluginOps {
+  static const char* check(const dial_model* m, const dial_derived* dv) {
+    (void)dv;
+    if (m->cone != DIAL_CONE_PYRAMIDAL) return "task plugins support pyramidal friction cones only (the model's cone is elliptic)";
+    if (kbi_unique_rows(m) > DIAL_KBI_ROWS) return "the model has more distinct (solref, solimp) rows than the impedance table holds (DIAL_KBI_ROWS)";
+    if (!dims_match<D>(m)) return "the model's dimensions differ from the plugin's (rebuild the plugin for this model)";
+    return nullptr;
+  }
+  // dial_create's `upload` for the generic feature set at compile-time dimensions (dial_hip.hip)
+  static int layout(const dial_model* model, const dial_cfg* cfg, int opt_con_cap, dial_plugin_layout* out) {
+    Ws s;
+    const int nnode = cfg ? cfg->Hnode + 1 : 0;
+    out->ws0_words = ws_carve(s, (float*)0, model->nq, model->nv, model->nu, model->nbody, model->njnt, model->ngeom, model->nsite,
+                              model->ncon, model->nefc, 0, dial::kNeedL<D>, D::square, 0, 0, D::NVP);
+    out->cm_bytes = (int)(((sizeof(CModel<D>) + 15) / 16) * 16);
+    out->con_cap = 0;
+    out->ovf_words = 0;
+    const bool given = opt_con_cap != 0;
+    int cap = given ? opt_con_cap : 14;
+    if (cfg && cap > 0 && model->ncon > cap) {
+      if (!given) {   // the largest cap in 20 .. 4 with which NINE wavefronts (and their constants) fit a CU
+        const size_t budget = WPB > 1 ? ((size_t)160 * 1024 / (9 / WPB) - out->cm_bytes) / WPB / 16 * 16
+                                      : ((size_t)160 * 1024 / 9 - out->cm_bytes) / 16 * 16;
+        for (int c = 20; c >= 4; c--) {
+          Ws st;
+          const int wds = ws_carve(st, (float*)0, model->nq, model->nv, model->nu, model->nbody, model->njnt, model->ngeom, model->nsite,
+                                   model->ncon, model->nefc, nnode, dial::kNeedL<D>, D::square, 0, c, D::NVP);
+          cap = c;
+          if ((size_t)wds * sizeof(float) <= budget) break;
+        }
+      }
+      out->con_cap = cap;
+      Ws so;
+      out->ovf_words = ws_overflow(so, (float*)0, model->nv, model->ncon, model->nefc);
+    }
+    out->ws_words = ws_carve(s, (float*)0, model->nq, model->nv, model->nu, model->nbody, model->njnt, model->ngeom, model->nsite,
+                             model->ncon, model->nefc, nnode, dial::kNeedL<D>, D::square, 0, out->con_cap, D::NVP, 0);
+    return DIAL_OK;
+  }
+  static void set_params(void* host_cm, const float* params, int n) {
+    CModel<D>* c = (CModel<D>*)host_cm;
+    for (int k = 0; k < DIAL_USER_PARAMS; k++) c->user_params[k] = (params && k < n) ? params[k] : 0.f;
+  }
+  static void fill(void* host_cm, const dial_model* m, const dial_task* t, const dial_derived* dv, const float* params, int n) {
+    CModel<D>* c = new (host_cm) CModel<D>();
+    fill_cmodel(c, m, t, dv);
+    set_params(c, params, n);
+  }
+  static hipError_t set_lds(size_t lds) {
+    if (lds <= 64 * 1024) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute((const void*)rollout_kernel<D, WPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rollout_kernel<D, WPB, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rollout_kernel<D, WPB, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return e;
+  }
+  static hipError_t occupancy(int* nb, size_t lds) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(nb, rollout_kernel<D, WPB>, 64 * WPB, lds); }
+  static hipError_t rollout(int variant, int blocks, size_t lds, hipStream_t st, const void* dcm, const dial_task* dtask, const dial_cfg* dcfg,
+                            const dial::RolloutIO* io, int B, int ws_words, int* next) {
+    const CModel<D>* cm = (const CModel<D>*)dcm;
+    if (variant == 2)
+      hipLaunchKernelGGL((rollout_kernel<D, WPB, 3, false, true>), dim3(blocks), dim3(64 * WPB), lds, st, cm, dtask, dcfg, *io, B, ws_words, (int*)nullptr);
+    else if (variant == 1)
+      hipLaunchKernelGGL((rollout_kernel<D, WPB, 3, true>), dim3(blocks), dim3(64 * WPB), lds, st, cm, dtask, dcfg, *io, B, ws_words, next);
+    else
+      hipLaunchKernelGGL((rollout_kernel<D, WPB, 3, false>), dim3(blocks), dim3(64 * WPB), lds, st, cm, dtask, dcfg, *io, B, ws_words, (int*)nullptr);
+    return hipGetLastError();
+  }
+  static hipError_t env_step(int n, size_t lds, hipStream_t st, const void* dcm, const dial_task* dtask, float* state, const float* action,
+                             float* xpos_out, float* xquat_out, float* ctrl_out) {
+    hipLaunchKernelGGL(env_step_kernel<D>, dim3(n), dim3(64), lds, st, (const CModel<D>*)dcm, dtask, state, action, xpos_out, xquat_out, ctrl_out);
+    return hipGetLastError();
+  }
+  static hipError_t env_reset(int n, size_t lds, hipStream_t st, const void* dcm, const float* qpos, const float* qvel, float* state,
+                              float* xpos_out, float* xquat_out) {
+    hipLaunchKernelGGL(env_reset_kernel<D>, dim3(n), dim3(64), lds, st, (const CModel<D>*)dcm, qpos, qvel, state, xpos_out, xquat_out);
+    return hipGetLastError();
+  }
+  static const dial_plugin_ops* table() {
+    static const dial_plugin_ops ops = {
+        DIAL_PLUGIN_ABI_VERSION,
+        {D::NQ, D::NV, D::NU, D::NB, D::NJ, D::NG, D::NS, D::NC, D::NL, D::NFRI},
+        WPB, sizeof(CModel<D>),
+        sizeof(dial_model), sizeof(dial_task), sizeof(dial_cfg), sizeof(dial_derived), sizeof(dial::RolloutIO),
+        &check, &layout, &fill, &set_params, &set_lds, &occupancy, &rollout, &env_step, &env_reset};
+    return &ops;
+  }
+};

@@ -216,6 +216,7 @@ DIAL_DEV void make_frame(float* fr, const float* a_in) {
 #include "smooth_rows.h"
 #include "solver_reg2.h"
 #include "smooth_quad2.h"
+#include "user_reward.h"
 namespace dial {
 
 // Generic instantiation: x = A^-1 rhs for the packed SPD matrix A (M or H) with the register-resident L D L^T of
@@ -1641,6 +1642,7 @@ DIAL_DEV void forward(W& w, const M* m, const Ws& s) {
 // Task kinds a kernel instantiation can be asked to run (the dimension-specialised ones are per robot; dial_create checks).
 template <class D>
 constexpr uint32_t task_kind_mask() {
+  if (D::user) return 1u << DIAL_TASK_USER;   // (a task plugin: the user reward only)
   if (std::is_same<D, DimsGo2Crate>::value) return 1u << DIAL_TASK_GO2_CRATE;   // (dispatched ahead of the reward phase)
   if (std::is_same<D, DimsH1PushCrate>::value) return 1u << DIAL_TASK_H1_PUSH_CRATE;
   if (std::is_same<typename D::Topo, TopoGo2>::value) return (1u << DIAL_TASK_GO2_WALK) | (1u << DIAL_TASK_GO2_SEQ_JUMP);
@@ -1819,6 +1821,22 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
     forward(w, m, s);
     euler(w, m, s);
     DIAL_MARK(w, 9);
+  }
+  if constexpr (M::D::user) {
+    // a task plugin's user reward (user_reward.h: contract, which quantities are pre- / post-integration), on one lane like the
+    // crate-climb reward below; dial_create_plugin admits DIAL_TASK_USER only
+    w.items(1, [&](int) {
+      float* info = s.info;
+      const float step = info[DIAL_INFO_STEP];
+      const DialRewardIn in{dim_nq(m), dim_nv(m), nu, dim_nb(m), dim_ns(m), dim_nc(m), step, m->dt,
+                            s.qpos, s.qvel, s.xpos, s.xquat, s.spos, s.cdist, s.cpos, s.ctrl, s.act};
+      const float reward = dial_user_reward(in, m->user_params, info + DIAL_INFO_USER);
+      if (FULL_INFO) info[DIAL_INFO_DONE] = 0.f;
+      info[DIAL_INFO_STEP] = step + 1.f;
+      info[DIAL_INFO_REWARD] = reward;
+    });
+    DIAL_MARK(w, 10);
+    return s.info[DIAL_INFO_REWARD];
   }
   if (m->kind == DIAL_TASK_ALLEGRO) {
     // manipulation.py:75-100 (torso_x = the object body): three sums of squares, one lane each

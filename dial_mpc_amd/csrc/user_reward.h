@@ -1,0 +1,42 @@
+// user_reward.h -- the contract of a user reward (DIAL_TASK_USER), the one function a custom environment writes in HIP.
+//
+//   DIAL_DEV float dial_user_reward(const DialRewardIn& in, const float* params, float* info_user);
+//
+// A task plugin (dial_mpc_amd/plugin.py) compiles it into the rollout / env.step / env.reset kernels of ONE model, at that model's
+// compile-time dimensions (cmodel.h: DimsUser).  It is evaluated once per control step, on ONE lane of the wavefront, after the
+// step's physics (rollout_body.h: env_step); its return value is the step's reward (info[DIAL_INFO_REWARD], the per-step rewards of a
+// rollout, the mean rewards that weight the samples).
+//
+// What it sees, and when (the rule every built-in reward follows -- brax's pipeline_state after mjx.step):
+//   POST-integration (the state the step ends in):  qpos [nq], qvel [nv]
+//   PRE-integration forward quantities (kinematics / collision of the state the step STARTED from, the last forward() before
+//   the integrator):                                 xpos [nbody][3], xquat [nbody][4] (w x y z), spos [nsite][3],
+//                                                    cdist [ncon], cpos [ncon][3] (per static contact slot of the model)
+//   the step's control:                              act [nu]  (the normalised action in [-1, 1] the planner chose)
+//                                                    ctrl [nu] (what was applied: torques, or joint targets under position control)
+//   step:  the step counter BEFORE this step (0 on the first step after env.reset); dt: the control step in seconds.
+// Body / site / contact indices are the model's own (body 0 is the world).  Every array is read-only.
+//   params:    the DIAL_USER_PARAMS task parameters (dial_create_plugin / dial_set_user_params; unset entries are zero).
+//   info_user: DIAL_INFO_USER_N read / write floats of the env info (slots DIAL_INFO_USER ...).  Zero after env.reset; they persist
+//              from step to step of a rollout and across env.step, like upstream's state.info.
+// The function must be deterministic and free of side effects beyond info_user: it runs in every sample of every rollout.
+#pragma once
+#include "../../include/dial_mpc.h"
+
+#ifndef DIAL_DEV
+#define DIAL_DEV __device__ __forceinline__
+#endif
+
+static_assert(DIAL_INFO_LAST_CTRL + DIAL_MAX_U <= DIAL_INFO_USER && DIAL_INFO_USER + DIAL_INFO_USER_N <= DIAL_INFO_N,
+              "the user slots of the env info overlap the built-in ones");
+
+struct DialRewardIn {
+  int nq, nv, nu, nbody, nsite, ncon;
+  float step, dt;
+  const float *qpos, *qvel;                       // post-integration
+  const float *xpos, *xquat, *spos, *cdist, *cpos;   // pre-integration forward quantities
+  const float *ctrl, *act;                        // the step's control
+};
+
+// defined by the plugin's reward source (the plugin's translation unit only; no kernel of libdialhip.so calls it)
+DIAL_DEV float dial_user_reward(const DialRewardIn& in, const float* params, float* info_user);

@@ -1,0 +1,90 @@
+"""``CustomEnv`` -- a user environment on the HIP path: the user's model, the user's reward (one HIP device function, the
+contract of csrc/user_reward.h) and a vector of float task parameters, compiled into a task plugin for that model
+(dial_mpc_amd/plugin.py) the first time the env plans or steps.
+
+A subclass sets
+  ``model_path``   an MJCF (compiled by dial_mpc_amd/mjcf.py) or a compiled-model JSON; relative paths are taken from the
+                   directory of the module that defines the subclass,
+  ``reward_hip``   the reward's HIP source, or the path of a ``.hip`` file (relative as above),
+  ``user_params``  names of float fields of its config dataclass; their values, in this order, are the reward's ``params``,
+  ``init_keyframe`` the model keyframe env.reset starts from (default "home"),
+and registers itself with ``dial_mpc_amd.envs.register_environment`` / ``register_config``.  Control is BaseEnv's
+(act2joint / act2tau with the config's leg_control, kp, kd, action_scale); the sampling range is the joint range of the model
+unless the subclass sets ``self.joint_range``.
+"""
+from __future__ import annotations
+
+import inspect
+import os
+from typing import Any, Dict, List, Sequence
+
+import numpy as np
+
+from dial_mpc_amd import _abi, mjcf
+from dial_mpc_amd.envs.base_env import BaseEnv, BaseEnvConfig, System
+
+TASK_USER = _abi.MACROS["DIAL_TASK_USER"]
+
+
+class CustomEnv(BaseEnv):
+    task_kind = TASK_USER
+    model_path: str = ""
+    reward_hip: str = ""
+    user_params: Sequence[str] = ()
+    init_keyframe: str = "home"
+
+    def __init__(self, config: BaseEnvConfig):
+        if not self.model_path or not self.reward_hip:
+            raise TypeError(f"{type(self).__name__}: a CustomEnv subclass sets model_path and reward_hip")
+        super().__init__(config)
+        self._init_q = np.asarray(self.sys.model["keyframes"][self.init_keyframe], dtype=np.float64)
+        self._plugin = None
+
+    @classmethod
+    def _resolve(cls, p: str) -> str:
+        if os.path.isabs(p):
+            return p
+        return os.path.join(os.path.dirname(os.path.abspath(inspect.getfile(cls))), p)
+
+    def make_system(self, config: BaseEnvConfig) -> System:
+        path = self._resolve(self.model_path)
+        model = mjcf.compile_mjcf(path) if path.endswith(".xml") else mjcf.model_from_json(open(path).read())
+        return System(model).tree_replace({"opt.timestep": config.timestep})
+
+    def reward_source(self) -> str:
+        src = self.reward_hip
+        if "\n" not in src and src.endswith(".hip"):
+            return open(self._resolve(src)).read()
+        return src
+
+    def user_param_vector(self) -> List[float]:
+        return [float(getattr(self._config, name)) for name in self.user_params]
+
+    def task_dict(self) -> Dict[str, Any]:
+        return dict(super().task_dict(), nfeet=0)
+
+    def plugin_path(self) -> str:
+        """Build (or find in the cache) this env's task plugin."""
+        if self._plugin is None:
+            from dial_mpc_amd.plugin import build_plugin
+            self._plugin = build_plugin(self.sys.model, self.reward_source())
+        return self._plugin
+
+    def context_kwargs(self) -> Dict[str, Any]:
+        """What a _lib.Context of this env needs beyond (model, task, cfg): its plugin and parameters."""
+        return dict(plugin=self.plugin_path(), user_params=self.user_param_vector())
+
+    def set_user_params(self, **values) -> None:
+        """Change config fields listed in user_params; contexts created from now on, and this env's own, use them."""
+        for k, v in values.items():
+            if k not in self.user_params:
+                raise KeyError(f"{k!r} is not one of {list(self.user_params)}")
+            setattr(self._config, k, float(v))
+        if self._ctx is not None:
+            self._ctx.set_user_params(self.user_param_vector())
+
+    def _context(self):
+        if self._ctx is None:
+            from dial_mpc_amd import _lib
+            self._ctx = _lib.Context(self.make_model(), self.make_task(), None, getattr(self, "_device", None), **self.context_kwargs())
+        return self._ctx

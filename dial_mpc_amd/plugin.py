@@ -1,0 +1,153 @@
+"""Task plugins: a user reward compiled, for one model, into the rollout / env.step / env.reset kernels (HIP, gfx950).
+
+``build_plugin(model, reward_src)`` writes the model's dimensions and the reward source next to ``csrc/plugin.hip``'s object,
+compiles that one translation unit with the product flags (``_lib._COMMON + _FAST``) and links a shared library that
+``libdialhip.so`` loads (``dial_create_plugin``; ``_lib.Context(..., plugin=path)``).  The reward's contract is in
+``csrc/user_reward.h``.  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
+hashes every csrc source, ``include/dial_mpc.h``, the reward, the dimensions, the flags and ``hipcc --version``.  hipcc
+cross-compiles, so building needs no GPU.
+"""
+from __future__ import annotations
+
+import glob
+import hashlib
+import os
+import re
+import shutil
+import subprocess
+from typing import Any, Dict, Optional, Sequence, Union
+
+import numpy as np
+
+from dial_mpc_amd import _abi
+from dial_mpc_amd._lib import _COMMON, _CSRC, _FAST, DialHipError
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOL = "dial_plugin_ops_v1"
+DIM_NAMES = ("nq", "nv", "nu", "nbody", "njnt", "ngeom", "nsite", "ncon", "nlim", "nfri")
+_DIM_MACROS = ("NQ", "NV", "NU", "NB", "NJ", "NG", "NS", "NC", "NL", "NFRI")
+
+
+def _kbi_rows_capacity() -> int:
+    m = re.search(r"#define\s+DIAL_KBI_ROWS\s+(\d+)", open(os.path.join(_CSRC, "cmodel.h")).read())
+    return int(m.group(1))
+
+
+def _model_dict(model: Union[Dict[str, Any], "_abi.DialModel"]) -> Dict[str, Any]:
+    if isinstance(model, dict):
+        return model
+    return {k: (_abi.as_numpy(model, k) if _abi.DialModel._meta[k][0] else getattr(model, k)) for k in _abi.DialModel._meta}
+
+
+def plugin_dims(model) -> Dict[str, int]:
+    """The compile-time dimensions a plugin for `model` (a compiled model dict or a DialModel) is instantiated with."""
+    d = _model_dict(model)
+    return {k: int(np.asarray(d.get(k, 0))) for k in DIM_NAMES}
+
+
+def kbi_unique_rows(model) -> int:
+    """Distinct (solref, solimp) rows among the limit rows, contacts and dry-friction rows (csrc/derived.h: kbi_unique_rows)."""
+    d = _model_dict(model)
+    rows = set()
+    f32 = lambda a: tuple(np.asarray(a, dtype=np.float32).ravel().tolist())   # noqa: E731
+
+    def add(ref, imp):
+        rows.add(f32(ref)[:2] + f32(imp)[:5])
+    for l in range(int(d["nlim"])):
+        j = int(np.asarray(d["lim_jnt"])[l])
+        add(np.asarray(d["jnt_solref"])[j], np.asarray(d["jnt_solimp"])[j])
+    for c in range(int(d["ncon"])):
+        add(np.asarray(d["con_solref"])[c], np.asarray(d["con_solimp"])[c])
+    for q in range(int(d.get("nfri", 0))):
+        add(np.asarray(d["fri_solref"])[q], np.asarray(d["fri_solimp"])[q])
+    return len(rows)
+
+
+def check_model(model) -> None:
+    """Raise DialHipError when a task plugin cannot serve `model` (csrc/plugin_ops.h: PluginOps::check)."""
+    d = _model_dict(model)
+    if int(d.get("cone", 0)) != _abi.MACROS["DIAL_CONE_PYRAMIDAL"]:
+        raise DialHipError("task plugins support pyramidal friction cones only: the model uses elliptic cones")
+    n, cap = kbi_unique_rows(d), _kbi_rows_capacity()
+    if n > cap:
+        raise DialHipError(f"the model has {n} distinct (solref, solimp) sets; the impedance table of a plugin holds "
+                           f"DIAL_KBI_ROWS = {cap}")
+
+
+def dims_header(model) -> str:
+    dims = plugin_dims(model)
+    return "".join(f"#define DIAL_PLUGIN_{m} {dims[k]}\n" for k, m in zip(DIM_NAMES, _DIM_MACROS))
+
+
+def _read_reward(reward_src: str) -> str:
+    if "\n" not in reward_src and reward_src.endswith(".hip") and os.path.isfile(reward_src):
+        return open(reward_src).read()
+    return reward_src
+
+
+def _hipcc() -> str:
+    return os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def cache_root() -> str:
+    return os.environ.get("DIAL_PLUGIN_CACHE", os.path.join(_ROOT, "build", "plugins"))
+
+
+def plugin_key(model, reward_src: str, flags: Sequence[str]) -> str:
+    h = hashlib.sha256()
+    for p in sorted(glob.glob(os.path.join(_CSRC, "*.h")) + glob.glob(os.path.join(_CSRC, "*.hip"))) + [_abi.HEADER]:
+        h.update(os.path.basename(p).encode() + b"\0" + open(p, "rb").read() + b"\0")
+    h.update(_read_reward(reward_src).encode() + b"\0")
+    h.update(dims_header(model).encode() + b"\0")
+    h.update(" ".join(flags).encode() + b"\0")
+    h.update(subprocess.run([_hipcc(), "--version"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout.encode())
+    return h.hexdigest()
+
+
+def build_plugin(model, reward_src: str, flags: Optional[Sequence[str]] = None, verbose: bool = False) -> str:
+    """Compile (or find in the cache) the task plugin of `model` with the reward `reward_src` (HIP source text, or the path of a
+    .hip file) -> path of the shared library.  A compile error raises DialHipError with hipcc's own message."""
+    import fcntl
+    check_model(model)
+    flags = list(_COMMON + _FAST if flags is None else flags)
+    reward = _read_reward(reward_src)
+    key = plugin_key(model, reward, flags)[:24]
+    root = cache_root()
+    out_dir = os.path.join(root, key)
+    out = os.path.join(out_dir, "libdialplugin.so")
+    if os.path.exists(out):
+        return out
+    os.makedirs(root, exist_ok=True)
+    with open(os.path.join(root, key + ".lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)   # one builder per key (processes that race find the finished library)
+        try:
+            if os.path.exists(out):
+                return out
+            work = os.path.join(root, f"tmp_{key}_{os.getpid()}")
+            os.makedirs(work, exist_ok=True)
+            try:
+                with open(os.path.join(work, "dial_plugin_dims.h"), "w") as f:
+                    f.write("// generated by dial_mpc_amd/plugin.py: the model's compile-time dimensions\n" + dims_header(model))
+                with open(os.path.join(work, "dial_user_reward.hip"), "w") as f:
+                    f.write(reward)
+                obj = os.path.join(work, "plugin.o")
+                cmd = [_hipcc()] + flags + ["-I", work, "-c", "-o", obj, os.path.join(_CSRC, "plugin.hip")]
+                if verbose:
+                    print(" ".join(cmd))
+                r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+                if r.returncode != 0:
+                    raise DialHipError(f"hipcc failed ({r.returncode}) on the task plugin:\n{r.stdout[-6000:]}")
+                so = os.path.join(work, "libdialplugin.so")
+                r = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, obj],
+                                   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+                if r.returncode != 0:
+                    raise DialHipError(f"linking the task plugin failed ({r.returncode}):\n{r.stdout[-4000:]}")
+                os.makedirs(out_dir, exist_ok=True)
+                for name in ("dial_plugin_dims.h", "dial_user_reward.hip"):   # (kept beside the library: what it was built from)
+                    shutil.copy(os.path.join(work, name), os.path.join(out_dir, name))
+                os.replace(so, out)
+                return out
+            finally:
+                shutil.rmtree(work, ignore_errors=True)
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)

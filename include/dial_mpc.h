@@ -116,6 +116,8 @@ extern "C" {
 #define DIAL_TASK_ALLEGRO 4
 #define DIAL_TASK_GO2_CRATE 5  /* UnitreeGo2CrateEnv.step (unitree_go2_env.py:679-795) */
 #define DIAL_TASK_H1_PUSH_CRATE 6  /* UnitreeH1PushCrateEnv.step (unitree_h1_env.py:418-566) */
+#define DIAL_TASK_USER 7       /* a user reward compiled into a task plugin (dial_create_plugin, csrc/user_reward.h) */
+#define DIAL_USER_PARAMS 32    /* float task parameters of a user reward (dial_set_user_params)                       */
 
 /* packed-state info slots (floats; integers are stored as exactly representable floats) */
 #define DIAL_INFO_STEP 0
@@ -129,6 +131,8 @@ extern "C" {
 #define DIAL_INFO_DONE 20
 #define DIAL_INFO_REWARD 21
 #define DIAL_INFO_LAST_CTRL 22    /* DIAL_MAX_U */
+#define DIAL_INFO_USER 42         /* 6: read / write slots of a user reward (DIAL_TASK_USER), zero after env.reset */
+#define DIAL_INFO_USER_N 6
 
 /* error codes */
 #define DIAL_OK 0
@@ -517,6 +521,19 @@ int dial_status(dial_ctx* ctx);
  * with DIAL_ERR_ARG.  This exposes the per-step qacc_warmstart and env info, so that the oracle can be restarted from the
  * GPU's OWN state after step t and compared with the GPU's step t + 1 (tests/conftest.py: transition_parity).          */
 int dial_set_state_trace(dial_ctx* ctx, float* trace, int rows);
+
+/* Custom environments: a context whose rollout / env.step / env.reset kernels come from a TASK PLUGIN -- a shared library built
+ * by dial_mpc_amd/plugin.py (hipcc --offload-arch=gfx950) for ONE model's compile-time dimensions with a user reward fused in
+ * (csrc/user_reward.h states the reward's contract).  task->kind must be DIAL_TASK_USER; the plugin's dimensions must equal the
+ * model's; pyramidal cones only, at most DIAL_KBI_ROWS distinct (solref, solimp) rows.  params:[n_params] (n_params <=
+ * DIAL_USER_PARAMS, the rest zero) are the reward's task parameters.  Every entry point above then runs on the context
+ * unchanged, except the sharded ones (dial_shard_*), which fail with DIAL_ERR_ARG.  dial_create / dial_create_ex refuse
+ * DIAL_TASK_USER.  Fails with DIAL_ERR_ARG / DIAL_ERR_UNSUPPORTED and a message (dial_last_error(NULL)) naming the reason. */
+int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task* task, const dial_cfg* cfg, int device,
+                       const dial_options* opts, const char* plugin_path, const float* params, int n_params);
+/* New task parameters for a plugin context (no rebuild): params:[n] host floats, n <= DIAL_USER_PARAMS, the rest zero.
+ * Synchronises the device; launches issued afterwards see the new values. */
+int dial_set_user_params(dial_ctx* ctx, const float* params, int n);
 
 /* ABI self-description used by tests: sizeof of the three structs. */
 int dial_abi_sizes(int* model_bytes, int* task_bytes, int* cfg_bytes);
