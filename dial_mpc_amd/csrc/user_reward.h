@@ -9,13 +9,23 @@
 //
 // What it sees, and when (the rule every built-in reward follows -- brax's pipeline_state after mjx.step):
 //   POST-integration (the state the step ends in):  qpos [nq], qvel [nv]
-//   PRE-integration forward quantities (kinematics / collision of the state the step STARTED from, the last forward() before
-//   the integrator):                                 xpos [nbody][3], xquat [nbody][4] (w x y z), spos [nsite][3],
+//   PRE-integration forward quantities (kinematics / collision of the last forward() before the integrator: the state the step
+//   started from when n_frames == 1, see below):     xpos [nbody][3], xquat [nbody][4] (w x y z), spos [nsite][3],
 //                                                    cdist [ncon], cpos [ncon][3] (per static contact slot of the model)
 //   the step's control:                              act [nu]  (the normalised action in [-1, 1] the planner chose)
 //                                                    ctrl [nu] (what was applied: torques, or joint targets under position control)
-//   step:  the step counter BEFORE this step (0 on the first step after env.reset); dt: the control step in seconds.
-// Body / site / contact indices are the model's own (body 0 is the world).  Every array is read-only.
+//   step:  the step counter BEFORE this step (0 on the first step after env.reset); dt: the control step in seconds
+//          (n_frames x timestep, fp32).
+// n_frames > 1 (a control step of several physics sub-steps): the pre-integration quantities are those of the LAST sub-step's
+// forward(), i.e. of the state before the last sub-step -- brax's pipeline_state after the last mjx.step.  They coincide with the
+// state the step started from only when n_frames == 1.
+// Body / site / contact indices are the model's own.  Body 0 is the world: xpos[0..2] = 0, xquat[0..3] = (1, 0, 0, 0); the robot's
+// first body is body 1.  Every array is read-only.
+// cdist / cpos hold every static contact slot, touching or not: the narrow phase's signed distance and midpoint, recomputed by
+// every forward() (never left over from an earlier step or sample).  One exception: a plane-box, capsule-box or box-box slot that
+// the broad phase puts more than 1 cm (DIAL_BOX_PARK_DIST) from touching is PARKED -- cdist is above 1 cm, either a lower bound of
+// the distance (the broad phase's gap) or 1.0; cpos is the box's centre for a plane-box slot and the midpoint of the two geoms'
+// centres for a capsule-box or box-box slot.  Compare cdist with a threshold below 1 cm; read cpos only for slots within it.
 //   params:    the DIAL_USER_PARAMS task parameters (dial_create_plugin / dial_set_user_params; unset entries are zero).
 //   info_user: DIAL_INFO_USER_N read / write floats of the env info (slots DIAL_INFO_USER ...).  Zero after env.reset; they persist
 //              from step to step of a rollout and across env.step, like upstream's state.info.

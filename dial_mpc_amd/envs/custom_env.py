@@ -10,7 +10,9 @@ A subclass sets
   ``init_keyframe`` the model keyframe env.reset starts from (default "home"),
 and registers itself with ``dial_mpc_amd.envs.register_environment`` / ``register_config``.  Control is BaseEnv's
 (act2joint / act2tau with the config's leg_control, kp, kd, action_scale); the sampling range is the joint range of the model
-unless the subclass sets ``self.joint_range``.
+unless the subclass sets ``self.joint_range``.  Under ``leg_control: torque`` the PD law reads actuator a's joint as qpos[7 + a] /
+qvel[6 + a] (BaseEnv.act2tau): the model must have a free base joint and actuators that drive dofs 6, 7, ... in order; a model
+that does not is refused (``torque_joint_convention``).
 """
 from __future__ import annotations
 
@@ -26,6 +28,22 @@ from dial_mpc_amd.envs.base_env import BaseEnv, BaseEnvConfig, System
 TASK_USER = _abi.MACROS["DIAL_TASK_USER"]
 
 
+def torque_joint_convention(model: Dict[str, Any]) -> None:
+    """Raise ValueError unless torque control's joint indexing fits `model`: the PD law of BaseEnv.act2tau (and of every kernel)
+    reads actuator a's joint position / velocity at qpos[7 + a] / qvel[6 + a], while the force goes to the actuator's own dof
+    (act_qposadr / act_dofadr) -- so the model needs a free base joint first and actuator a on qpos 7 + a, dof 6 + a."""
+    nu = int(model["nu"])
+    qadr = np.asarray(model["act_qposadr"]).ravel()[:nu]
+    dadr = np.asarray(model["act_dofadr"]).ravel()[:nu]
+    free = int(model["njnt"]) > 0 and int(np.asarray(model["jnt_type"]).ravel()[0]) == mjcf.JNT_FREE and int(np.asarray(model["jnt_qposadr"]).ravel()[0]) == 0
+    bad = [a for a in range(nu) if int(qadr[a]) != 7 + a or int(dadr[a]) != 6 + a]
+    if not free or bad:
+        what = "joint 0 is not a free base joint" if not free else (
+            f"actuator {bad[0]} drives qpos {int(qadr[bad[0]])} / dof {int(dadr[bad[0]])}")
+        raise ValueError("leg_control: torque needs actuator a to drive qpos[7 + a] / qvel[6 + a] after a free base joint (the joint "
+                         f"indexing of BaseEnv.act2tau); {what}.  Reorder the model's actuators or use leg_control: position")
+
+
 class CustomEnv(BaseEnv):
     task_kind = TASK_USER
     model_path: str = ""
@@ -37,6 +55,8 @@ class CustomEnv(BaseEnv):
         if not self.model_path or not self.reward_hip:
             raise TypeError(f"{type(self).__name__}: a CustomEnv subclass sets model_path and reward_hip")
         super().__init__(config)
+        if config.leg_control == "torque":
+            torque_joint_convention(self.sys.model)
         self._init_q = np.asarray(self.sys.model["keyframes"][self.init_keyframe], dtype=np.float64)
         self._plugin = None
 
