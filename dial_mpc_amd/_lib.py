@@ -12,6 +12,8 @@ import os
 import subprocess
 from typing import Optional
 
+import numpy as np
+
 from dial_mpc_amd import _abi
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
@@ -175,6 +177,11 @@ def load(path: Optional[str] = None):
     except AttributeError:
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack the task-plugin entry points)
             raise
+    try:
+        lib.dial_set_plan_params.argtypes = [vp, fp, ci]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack per-plan task parameters)
+            raise
     lib.dial_env_reset.argtypes = [vp, fp, fp, fp, fp, fp, vp]
     lib.dial_env_reset_batch.argtypes = [vp, fp, fp, fp, fp, fp, ci, vp]
     lib.dial_status.argtypes = [vp]
@@ -196,7 +203,23 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
             "dial_shard_ybar_gathered", "dial_shard_ybar_gathered_rng", "dial_shard_reduce_gathered", "dial_shift", "dial_env_step", "dial_env_reset", "dial_env_reset_batch",
             "dial_status", "dial_set_timing", "dial_get_rollout_ms", "dial_abi_sizes",
             "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch",
-            "dial_create_plugin", "dial_set_user_params")
+            "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params")
+
+
+def plan_param_rows(rows) -> np.ndarray:
+    """Per-plan task parameters as dial_set_plan_params takes them: `rows` [M, n] (array, nested list or tensor; n <= DIAL_USER_PARAMS)
+    -> float32 [M, DIAL_USER_PARAMS], each row padded with zeros.  Raises ValueError on another shape."""
+    if hasattr(rows, "detach"):
+        rows = rows.detach().cpu().numpy()
+    a = np.asarray(rows, dtype=np.float32)
+    cap, max_plans = _abi.MACROS["DIAL_USER_PARAMS"], _abi.MACROS["DIAL_MAX_PLANS"]
+    if a.ndim != 2 or a.shape[1] > cap:
+        raise ValueError(f"per-plan task parameters are [M, n] rows with n <= DIAL_USER_PARAMS = {cap}; got shape {a.shape}")
+    if not 1 <= a.shape[0] <= max_plans:
+        raise ValueError(f"per-plan task parameters: {a.shape[0]} rows; 1 .. DIAL_MAX_PLANS = {max_plans} are allowed")
+    out = np.zeros((a.shape[0], cap), np.float32)
+    out[:, :a.shape[1]] = a
+    return out
 
 
 def _ptr(t) -> Optional[int]:
@@ -274,6 +297,25 @@ class Context:
         p = self._params(vals)
         n = len(vals)
         self._check(self.lib.dial_set_user_params(self.h, ctypes.addressof(p), n), "dial_set_user_params")
+
+    def set_plan_params(self, rows):
+        """Per-plan task parameters of a task-plugin context (dial_set_plan_params): `rows` [M, n] (n <= DIAL_USER_PARAMS; host array
+        or tensor, padded with zeros) -- plan g of a grouped launch / state g of env_step_batch reads row g, single-plan launches row 0.
+        The device copy stays alive while bound.  None unbinds: the shared parameters (set_user_params) apply again."""
+        import torch
+        if rows is None:
+            self._check(self.lib.dial_set_plan_params(self.h, None, 0), "dial_set_plan_params")
+            self._plan_params = None
+            return None
+        cap = _abi.MACROS["DIAL_USER_PARAMS"]
+        if (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] == cap
+                and rows.is_contiguous() and rows.device == self.torch_device):
+            dev = rows   # (already in the binding's layout: no copy)
+        else:
+            dev = torch.as_tensor(plan_param_rows(rows), device=self.torch_device)
+        self._check(self.lib.dial_set_plan_params(self.h, dev.data_ptr(), int(dev.shape[0])), "dial_set_plan_params")
+        self._plan_params = dev
+        return dev
 
     def __del__(self):
         try:

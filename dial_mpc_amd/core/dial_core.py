@@ -177,14 +177,23 @@ class MBDPI:
                                     eps.contiguous() if eps is not None else None, want_bars, plan=self._plan, rng=rng)
 
     # ---- M independent plans in one launch: jax.vmap(reverse_once) over (state, rng, Ybar_i, noise_scale)
-    def reverse_once_batch(self, states, rng, Ybars, noise_scales, eps=None, want_bars: bool = True):
+    def reverse_once_batch(self, states, rng, Ybars, noise_scales, eps=None, want_bars: bool = True, user_params=None):
         """states: list of M States or packed [M, state_size]; Ybars [M, Hnode+1, nu]; noise_scales [M, ns] (or [ns]: the same for all).
         eps [M, N, Hnode+1, nu] explicit noise; None: kernel_rng -> in-kernel Philox (plan g draws global samples g N ..), else
-        torch.randn from `rng`.  Returns (rng, Ybar [M, Hnode+1, nu], info) with info rews [M, N+1], qbar / qdbar [M, T, .],
-        xbar [M, T, nbody-1, 3] (None with want_bars=False) and new_noise_scale."""
+        torch.randn from `rng`.  user_params: per-plan task parameters [M, n] of a custom environment (CustomEnv.plan_params), plan g's
+        reward reads row g -- bound on this planner's context for this call only.  Returns (rng, Ybar [M, Hnode+1, nu], info) with
+        info rews [M, N+1], qbar / qdbar [M, T, .], xbar [M, T, nbody-1, 3] (None with want_bars=False) and new_noise_scale."""
         import torch
         if self.world > 1 or self._force_sharded:
             raise NotImplementedError("reverse_once_batch: grouped plans run on one rank (sharded batches are not supported)")
+        if user_params is not None:
+            if self.ctx.plugin is None:
+                raise ValueError("reverse_once_batch: per-plan task parameters (user_params=) need a custom environment's task plugin")
+            self.ctx.set_plan_params(user_params)
+            try:
+                return self.reverse_once_batch(states, rng, Ybars, noise_scales, eps=eps, want_bars=want_bars)
+            finally:
+                self.ctx.set_plan_params(None)
         if isinstance(states, (list, tuple)):
             states = torch.stack([_packed(st) for st in states])
         states = torch.as_tensor(states, dtype=torch.float32, device=self.device).contiguous()
@@ -261,6 +270,34 @@ def _positive_int(v: str) -> int:
     return n
 
 
+def _env_params(parser, args, env):
+    """--env-param NAME=V1,...,VM -> {NAME: [V1 .. VM]}, checked against the env and --n-envs before anything runs."""
+    if not args.env_param:
+        return None
+    if not hasattr(env, "plan_params"):
+        parser.error(f"--env-param: {type(env).__name__} is a built-in environment; per-loop task parameters need a custom environment")
+    if args.n_envs < 2:
+        parser.error("--env-param needs --n-envs M with M > 1 (one closed loop takes its parameters from the config)")
+    out = {}
+    for item in args.env_param:
+        name, sep, vals = item.partition("=")
+        name = name.strip()
+        try:
+            values = [float(v) for v in vals.split(",")] if sep and vals.strip() else None
+        except ValueError:
+            values = None
+        if not name or values is None:
+            parser.error(f"--env-param {item!r}: expected NAME=V1,...,VM")
+        if name not in env.user_params:
+            parser.error(f"--env-param: {name!r} is not one of the task parameters {list(env.user_params)}")
+        if len(values) != args.n_envs:
+            parser.error(f"--env-param {name}: {len(values)} values for --n-envs {args.n_envs}")
+        if name in out:
+            parser.error(f"--env-param {name} given twice")
+        out[name] = values
+    return out
+
+
 def main(argv=None):
     """Synchronous simulation driver: the body of the reference's ``main`` (dial_core.py:175-329).
     ``--n-envs M`` (M > 1) runs M closed loops through the grouped entry points (main_batched)."""
@@ -278,6 +315,8 @@ def main(argv=None):
     parser.add_argument("--n-steps", type=int, default=None, help="override n_steps from the YAML")
     parser.add_argument("--n-envs", type=_positive_int, default=1,
                         help="M closed loops from env.reset, planned together in one launch per iteration (default 1)")
+    parser.add_argument("--env-param", action="append", default=[], metavar="NAME=V1,...,VM",
+                        help="custom environments with --n-envs M: closed loop g runs with task parameter NAME = Vg (repeatable)")
     args = parser.parse_args(argv)
 
     if args.list_examples:
@@ -295,7 +334,10 @@ def main(argv=None):
     dial_config, env_config, env = load_dial_and_env(config_dict)
     if args.n_steps is not None:
         dial_config.n_steps = args.n_steps
+    env_params = _env_params(parser, args, env)
     if args.n_envs > 1:
+        if env_params:
+            return main_batched(dial_config, env, args.n_envs, env_params=env_params)
         return main_batched(dial_config, env, args.n_envs)
     print("Creating environment")
     mbdpi = MBDPI(dial_config, env)
@@ -335,18 +377,26 @@ def main(argv=None):
     np.save(os.path.join(dial_config.output_dir, f"{timestamp}_predictions"), pred_arr)
 
 
-def batched_loop(mbdpi: "MBDPI", env, states, n_steps: int, eps_fn=None, on_tick=None):
+def batched_loop(mbdpi: "MBDPI", env, states, n_steps: int, eps_fn=None, on_tick=None, user_params=None):
     """M closed loops of the synchronous driver, planned together: per tick env.step of all M states (one launch), shift of all M
     plans, then Ndiffuse grouped annealing iterations.  eps_fn(t, i) -> eps [M, N, Hnode+1, nu] or None (noise from the planner's rng
-    / kernel_rng).  Returns (rollouts: per tick the list of M States, infos: per tick the last iteration's info, tick ms)."""
+    / kernel_rng).  user_params: per-loop task parameters [M, n] of a custom environment (CustomEnv.plan_params), loop g's env.step and
+    plan read row g.  Returns (rollouts: per tick the list of M States, infos: per tick the last iteration's info, tick ms)."""
     import torch
+    from dial_mpc_amd import _lib
     dc = mbdpi.args
     M = len(states)
+    step_kw, plan_kw = {}, {}
+    if user_params is not None:   # (padded device rows, converted once: each call binds them without a copy)
+        rows = torch.as_tensor(_lib.plan_param_rows(user_params), device=mbdpi.device)
+        if rows.shape[0] != M:
+            raise ValueError(f"batched_loop: {rows.shape[0]} rows of task parameters for {M} closed loops")
+        step_kw, plan_kw = dict(user_params=rows), dict(user_params=rows)
     rng = _generator(dc.seed, mbdpi.device)
     Y0 = torch.zeros((M, dc.Hnode + 1, mbdpi.nu), dtype=torch.float32, device=mbdpi.device)
     rollouts, infos, tick_ms = [], [], []
     for t in range(n_steps):
-        states = env.step_batch(states, Y0[:, 0])
+        states = env.step_batch(states, Y0[:, 0], **step_kw)
         rollouts.append(states)
         t0 = time.time()
         Y0 = mbdpi.shift_batch(Y0)
@@ -355,7 +405,7 @@ def batched_loop(mbdpi: "MBDPI", env, states, n_steps: int, eps_fn=None, on_tick
         info = None
         for i in range(n_diffuse):
             eps = eps_fn(t, i) if eps_fn is not None else None
-            rng, Y0, info = mbdpi.reverse_once_batch(states, rng, Y0, factors[i], eps=eps, want_bars=(i == n_diffuse - 1))
+            rng, Y0, info = mbdpi.reverse_once_batch(states, rng, Y0, factors[i], eps=eps, want_bars=(i == n_diffuse - 1), **plan_kw)
         torch.cuda.synchronize()
         mbdpi.ctx.status()
         tick_ms.append((time.time() - t0) * 1e3)
@@ -365,16 +415,18 @@ def batched_loop(mbdpi: "MBDPI", env, states, n_steps: int, eps_fn=None, on_tick
     return rollouts, infos, tick_ms
 
 
-def main_batched(dial_config, env, n_envs: int):
-    """``--n-envs M``: M closed loops from env.reset, each with its own plan noise, planned in one launch per annealing iteration."""
+def main_batched(dial_config, env, n_envs: int, env_params=None):
+    """``--n-envs M``: M closed loops from env.reset, each with its own plan noise, planned in one launch per annealing iteration.
+    env_params: {name: [M values]} -- per-loop task parameters of a custom environment (``--env-param``)."""
     print(f"Creating environment ({n_envs} closed loops, planned together)")
+    rows = env.plan_params(**env_params) if env_params else None
     mbdpi = MBDPI(dial_config, env, n_plans=n_envs)
     states = [env.reset() for _ in range(n_envs)]
 
     def on_tick(t, sts, ms):
         if t % 20 == 0:
             print(f"step {t:4d}  rew {[round(float(s.reward), 3) for s in sts]}  tick {ms:.2f} ms")
-    rollouts, infos, tick_ms = batched_loop(mbdpi, env, states, dial_config.n_steps, on_tick=on_tick)
+    rollouts, infos, tick_ms = batched_loop(mbdpi, env, states, dial_config.n_steps, on_tick=on_tick, user_params=rows)
     for e in range(n_envs):
         print(f"env {e}: mean reward = {np.mean([float(r[e].reward) for r in rollouts]):.2e}")
     if len(tick_ms) > 1:

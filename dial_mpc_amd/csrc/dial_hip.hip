@@ -27,8 +27,8 @@
 // the kernels are compiled in their own translation units, one per robot family (kern_family.hip, built in parallel)
 #define DIAL_X(D, WPB, OCC, Q, TR) \
   extern template __global__ void rollout_kernel<D, WPB, OCC, Q, TR>(const CModel<D>*, const dial_task*, const dial_cfg*, dial::RolloutIO, int, int, int*);
-#define DIAL_XE(D)                                                                                                              \
-  extern template __global__ void env_step_kernel<D>(const CModel<D>*, const dial_task*, float*, const float*, float*, float*, float*); \
+#define DIAL_XE(D)                                                                                                                                    \
+  extern template __global__ void env_step_kernel<D>(const CModel<D>*, const dial_task*, float*, const float*, float*, float*, float*, const float*); \
   extern template __global__ void env_reset_kernel<D>(const CModel<D>*, const float*, const float*, float*, float*, float*);
 DIAL_KERNELS_ALL(DIAL_X, DIAL_XE)
 #define DIAL_X2(D, WPB, OCC, Q, MI) \
@@ -344,6 +344,8 @@ struct dial_ctx {
                               // 7 a task plugin's instantiation (dial_create_plugin: `plug`)
   const dial_plugin_ops* plug = nullptr;   // inst 7: the plugin's host functions (the library stays loaded for the process)
   std::vector<char> plug_cm;               // inst 7: host copy of the constants (dial_set_user_params rewrites the parameters)
+  const float* plan_params = nullptr;      // inst 7: per-plan task parameters (dial_set_plan_params), caller-owned device rows ...
+  int plan_rows = 0;                       // ... [plan_rows, DIAL_USER_PARAMS]; nullptr: every launch reads the shared ones
   void* dcm = nullptr;        // CModel<D> of the chosen instantiation (device)
   dial_task* dtask = nullptr;
   dial_cfg* dcfg = nullptr;
@@ -465,8 +467,12 @@ int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task*
   dial_plugin_entry entry = (dial_plugin_entry)dlsym(h, DIAL_PLUGIN_SYMBOL);
   if (!entry) return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + plugin_path + " does not export " DIAL_PLUGIN_SYMBOL);
   const dial_plugin_ops* ops = entry();
-  if (!ops || ops->abi_version != DIAL_PLUGIN_ABI_VERSION || ops->sizeof_model != sizeof(dial_model) || ops->sizeof_task != sizeof(dial_task) ||
-      ops->sizeof_cfg != sizeof(dial_cfg) || ops->sizeof_derived != sizeof(dial_derived) || ops->sizeof_io != sizeof(dial::RolloutIO))
+  if (!ops) return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + plugin_path + ": " DIAL_PLUGIN_SYMBOL " returned no table");
+  if (ops->abi_version != DIAL_PLUGIN_ABI_VERSION)
+    return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: stale plugin: it reports plugin ABI version ") + std::to_string(ops->abi_version) +
+                                       ", the library needs version " + std::to_string(DIAL_PLUGIN_ABI_VERSION) + " (rebuild it from the current sources)");
+  if (ops->sizeof_model != sizeof(dial_model) || ops->sizeof_task != sizeof(dial_task) || ops->sizeof_cfg != sizeof(dial_cfg) ||
+      ops->sizeof_derived != sizeof(dial_derived) || ops->sizeof_io != sizeof(dial::RolloutIO))
     return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin was built against another version of the library (ABI mismatch; rebuild it)");
   if (model->cone != DIAL_CONE_PYRAMIDAL)
     return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: task plugins support pyramidal friction cones only (the model's cone is elliptic)");
@@ -485,6 +491,28 @@ int dial_set_user_params(dial_ctx* ctx, const float* params, int n) {
   ctx->plug->set_params(ctx->plug_cm.data(), params, n);
   HIP_TRY(ctx, hipDeviceSynchronize());   // (launches in flight read the constants)
   HIP_TRY(ctx, hipMemcpy(ctx->dcm, ctx->plug_cm.data(), ctx->plug->cmodel_bytes, hipMemcpyHostToDevice));
+  return DIAL_OK;
+}
+
+int dial_set_plan_params(dial_ctx* ctx, const float* params, int rows) {
+  if (!ctx) return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_params: null context");
+  if (!ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_params: the context has no task plugin (dial_create_plugin): per-plan task parameters "
+                                                 "are a task plugin's");
+  if (ctx->has_cfg && ctx->B_cap < ctx->hc.Nsample + 1)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_params: the context is sharded (n_local_cap < Nsample)");
+  if (params && (rows < 1 || rows > DIAL_MAX_PLANS))
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_params: rows = " + std::to_string(rows) + " is outside 1 .. DIAL_MAX_PLANS");
+  // (no synchronisation: launches read the pointer when they are issued, the rows when they run -- the caller keeps them alive)
+  ctx->plan_params = params;
+  ctx->plan_rows = params ? rows : 0;
+  return DIAL_OK;
+}
+
+// launches of M plans / states on a context with bound per-plan parameters need a row for each
+static int check_plan_rows(dial_ctx* ctx, int M, const char* who) {
+  if (ctx->plan_params && M > ctx->plan_rows)
+    return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": M = " + std::to_string(M) + " exceeds the " + std::to_string(ctx->plan_rows) +
+                                   " rows of per-plan task parameters bound with dial_set_plan_params");
   return DIAL_OK;
 }
 
@@ -953,6 +981,7 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
   // mean-trajectory relay (one wavefront per workgroup, the launch's last rollout is the mean trajectory, everything is
   // resident): the "+1" rollout runs as ceil(T / 2) two-step pieces on as many SIMDs instead of one more wavefront on one
   dial::RolloutIO io = io_in;
+  io.plan_params = ctx->plan_params;   // (task plugins; nullptr elsewhere: dial_set_plan_params refuses other contexts)
   io.con_cap = ctx->ovf ? ctx->con_cap : 0;
   io.ovf = ctx->ovf;
   io.ovf_words = ctx->ovf_words;
@@ -1308,6 +1337,7 @@ static int reverse_once_batch_impl(dial_ctx* ctx, const float* states, const flo
   if (ctx->B_cap < N + 1) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": the context is sharded (n_local_cap < Nsample); grouped plans need the whole batch");
   if (ns != 1 && ns != ctx->Hn1) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": ns = " + std::to_string(ns) + " must be 1 or Hnode+1 = " + std::to_string(ctx->Hn1));
   if (!states || !Ybar_in || !noise_scale || (!eps && !use_rng) || !Ybar_out || !rews) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": null argument");
+  if (int rc = check_plan_rows(ctx, M, who)) return rc;
   if (M == 1)
     return reverse_once_impl(ctx, states, Ybar_in, noise_scale, ns, eps, use_rng, seed, counter, Ybar_out, rews, qbar, qdbar, xbar, stream, who);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1358,18 +1388,20 @@ int dial_shift(dial_ctx* ctx, float* Y, void* stream) {
 static int env_step_launch(dial_ctx* ctx, float* state, const float* action, float* xpos_out, float* xquat_out,
                            float* ctrl_out, int n, void* stream, const char* who) {
   if (!ctx || !state || !action || n < 1) return fail(ctx, DIAL_ERR_ARG, who);
+  if (int rc = check_plan_rows(ctx, n, n > 1 ? "dial_env_step_batch" : "dial_env_step")) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
 #define DIAL_LAUNCH_STEP(D)                                                                                         \
   hipLaunchKernelGGL(env_step_kernel<D>, dim3(n), dim3(64), ctx->lds_bytes, (hipStream_t)stream,                   \
                      (const CModel<D>*)ctx->dcm, (const dial_task*)ctx->dtask, state, action, xpos_out, xquat_out, \
-                     ctrl_out)
+                     ctrl_out, (const float*)nullptr)
   if (ctx->inst == 1) DIAL_LAUNCH_STEP(DimsGo2);
   else if (ctx->inst == 2) DIAL_LAUNCH_STEP(DimsH1);
   else if (ctx->inst == 3) DIAL_LAUNCH_STEP(DimsH1Loco);
   else if (ctx->inst == 4) DIAL_LAUNCH_STEP(DimsAllegro);
   else if (ctx->inst == 5) DIAL_LAUNCH_STEP(DimsGo2Crate);
   else if (ctx->inst == 6) DIAL_LAUNCH_STEP(DimsH1PushCrate);
-  else if (ctx->inst == 7) HIP_TRY(ctx, ctx->plug->env_step(n, ctx->lds_bytes, (hipStream_t)stream, ctx->dcm, ctx->dtask, state, action, xpos_out, xquat_out, ctrl_out));
+  else if (ctx->inst == 7) HIP_TRY(ctx, ctx->plug->env_step(n, ctx->lds_bytes, (hipStream_t)stream, ctx->dcm, ctx->dtask, state, action, xpos_out, xquat_out, ctrl_out,
+                                                                ctx->plan_params));
   else DIAL_LAUNCH_STEP(DimsMax);
 #undef DIAL_LAUNCH_STEP
   HIP_TRY(ctx, hipGetLastError());

@@ -2,8 +2,8 @@
 #include "kernel_list.h"
 #define DIAL_X(D, WPB, OCC, Q, TR) \
   template __global__ void rollout_kernel<D, WPB, OCC, Q, TR>(const CModel<D>*, const dial_task*, const dial_cfg*, dial::RolloutIO, int, int, int*);
-#define DIAL_XE(D)                                                                                                       \
-  template __global__ void env_step_kernel<D>(const CModel<D>*, const dial_task*, float*, const float*, float*, float*, float*); \
+#define DIAL_XE(D)                                                                                                                             \
+  template __global__ void env_step_kernel<D>(const CModel<D>*, const dial_task*, float*, const float*, float*, float*, float*, const float*); \
   template __global__ void env_reset_kernel<D>(const CModel<D>*, const float*, const float*, float*, float*, float*);
 #define DIAL_X2(D, WPB, OCC, Q, MI) \
   template __global__ void rollout_kernel2<D, WPB, OCC, Q, MI>(const CModel<D>*, const dial_task*, const dial_cfg*, dial::RolloutIO, int, int, int*);

@@ -18,7 +18,8 @@ template __global__ void rollout_kernel<DimsPlugin, DIAL_PLUGIN_WPB, 3, true, fa
                                                                                  dial::RolloutIO, int, int, int*);
 template __global__ void rollout_kernel<DimsPlugin, DIAL_PLUGIN_WPB, 3, false, true>(const CModel<DimsPlugin>*, const dial_task*, const dial_cfg*,
                                                                                  dial::RolloutIO, int, int, int*);
-template __global__ void env_step_kernel<DimsPlugin>(const CModel<DimsPlugin>*, const dial_task*, float*, const float*, float*, float*, float*);
+template __global__ void env_step_kernel<DimsPlugin>(const CModel<DimsPlugin>*, const dial_task*, float*, const float*, float*, float*, float*,
+                                                      const float*);
 template __global__ void env_reset_kernel<DimsPlugin>(const CModel<DimsPlugin>*, const float*, const float*, float*, float*, float*);
 
 extern "C" __attribute__((visibility("default"))) const dial_plugin_ops* dial_plugin_ops_v1(void) {

@@ -13,7 +13,8 @@
 
 #include "rollout_kernel.h"
 
-#define DIAL_PLUGIN_ABI_VERSION 1
+// 2: env_step takes the per-state task parameters, RolloutIO gained plan_params (dial_set_plan_params)
+#define DIAL_PLUGIN_ABI_VERSION 2
 #define DIAL_PLUGIN_SYMBOL "dial_plugin_ops_v1"
 
 // what dial_create's `upload` computes for an instantiation: LDS layout and the generic feature set's contact cap
@@ -42,8 +43,9 @@ struct dial_plugin_ops {
   // variant 0 plain grid, 1 rollout queue (next != nullptr), 2 state trace
   hipError_t (*rollout)(int variant, int blocks, size_t lds, hipStream_t st, const void* dcm, const dial_task* dtask, const dial_cfg* dcfg,
                         const dial::RolloutIO* io, int B, int ws_words, int* next);
+  // plan_params: [n, DIAL_USER_PARAMS] per-state task parameters (state b reads row b), or nullptr (the shared ones)
   hipError_t (*env_step)(int n, size_t lds, hipStream_t st, const void* dcm, const dial_task* dtask, float* state, const float* action,
-                         float* xpos_out, float* xquat_out, float* ctrl_out);
+                         float* xpos_out, float* xquat_out, float* ctrl_out, const float* plan_params);
   hipError_t (*env_reset)(int n, size_t lds, hipStream_t st, const void* dcm, const float* qpos, const float* qvel, float* state,
                           float* xpos_out, float* xquat_out);
 };
@@ -120,8 +122,9 @@ struct PluginOps {
     return hipGetLastError();
   }
   static hipError_t env_step(int n, size_t lds, hipStream_t st, const void* dcm, const dial_task* dtask, float* state, const float* action,
-                             float* xpos_out, float* xquat_out, float* ctrl_out) {
-    hipLaunchKernelGGL(env_step_kernel<D>, dim3(n), dim3(64), lds, st, (const CModel<D>*)dcm, dtask, state, action, xpos_out, xquat_out, ctrl_out);
+                             float* xpos_out, float* xquat_out, float* ctrl_out, const float* plan_params) {
+    hipLaunchKernelGGL(env_step_kernel<D>, dim3(n), dim3(64), lds, st, (const CModel<D>*)dcm, dtask, state, action, xpos_out, xquat_out, ctrl_out,
+                       plan_params);
     return hipGetLastError();
   }
   static hipError_t env_reset(int n, size_t lds, hipStream_t st, const void* dcm, const float* qpos, const float* qvel, float* state,

@@ -100,6 +100,17 @@ DIAL_DEV void rollout_sample(W& w, const M* m, const dial_task* tg, const dial_c
   int g = 0, nl = n;
   if (io.plan_rollouts) { g = n / io.plan_rollouts; nl = n - g * io.plan_rollouts; }
   const float* const Ybar = io.Ybar + (size_t)g * Hn1 * nu;
+  if constexpr (M::D::user) {
+    // per-plan task parameters (io.plan_params): the staged constants in LDS belong to this wavefront alone (a task plugin's rollout
+    // kernel has one wavefront per workgroup, rollout_kernel asserts it), so plan g's row overwrites their user_params before the
+    // rollout's first step.  Every rollout item does this (a queue wavefront runs rollouts of different plans one after another);
+    // the reward call and the workspace stay as they are.
+    if (io.plan_params) {
+      float* const up = const_cast<float*>(m->user_params);
+      const float* const row = io.plan_params + (size_t)g * DIAL_USER_PARAMS;
+      w.items(DIAL_USER_PARAMS, [&](int k) { up[k] = row[k]; });
+    }
+  }
   if (relay <= 0) load_state(w, m, s, io.state + (size_t)g * (nq + 2 * nv + DIAL_INFO_N));
   if (!io.us) {
     // K1: candidate nodes (dial_core.py:110-115)

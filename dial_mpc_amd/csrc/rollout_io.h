@@ -64,6 +64,9 @@ struct RolloutIO {
   // draws the noise of global sample g x n_noise + local index (eps row, Philox key).  The plans' inputs are dense ([plans, ...]);
   // the outputs are indexed by the batch rollout n as in one-plan launches.
   int plan_rollouts;
+  // task plugins (Dims::user instantiations only; no other kernel reads it): per-plan task parameters (dial_set_plan_params),
+  // [rows, DIAL_USER_PARAMS] -- plan g's reward reads row g (row 0 in one-plan launches); nullptr: the shared CModel::user_params
+  const float* plan_params;
 };
 
 }  // namespace dial

@@ -45,6 +45,8 @@ template <class D, int WPB, int OCC = 3, bool QUEUE = false, bool TRACE = false>
 __global__ void __launch_bounds__(64 * WPB, OCC)
 rollout_kernel(const CModel<D>* __restrict__ gm, const dial_task* __restrict__ tg,
                const dial_cfg* __restrict__ cfg, dial::RolloutIO io, int B, int ws_words, int* __restrict__ next) {
+  // (task plugins: rollout_sample writes the plan's task parameters into the staged constants -- one copy per wavefront only)
+  static_assert(!D::user || WPB == 1, "per-plan task parameters overwrite the staged constants: one wavefront per workgroup");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   Ws s;
   const CModel<D>* m = stage_model<D, WPB>(gm, smem, s, io.Hn1, ws_words, io.con_cap, io.T);
@@ -202,7 +204,7 @@ rollout_kernel2(const CModel<D>* __restrict__ gm, const dial_task* __restrict__ 
 template <class D>
 __global__ void __launch_bounds__(64)
 env_step_kernel(const CModel<D>* __restrict__ gm, const dial_task* __restrict__ tg, float* state,
-                const float* action, float* xpos_out, float* xquat_out, float* ctrl_out) {
+                const float* action, float* xpos_out, float* xquat_out, float* ctrl_out, const float* plan_params) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   Ws s;
   const CModel<D>* m = stage_model<D>(gm, smem, s, 0, 0);
@@ -212,6 +214,13 @@ env_step_kernel(const CModel<D>* __restrict__ gm, const dial_task* __restrict__ 
   w.launder = D::gen;
   // (dial_env_step_batch: workgroup b steps state b of a batch -- rows of state / action / the optional outputs)
   const int b = (int)blockIdx.x, nq = dim_nq(m), nv = dim_nv(m), nu = dim_nu(m), nb1 = dim_nb(m) - 1;
+  // task plugins, per-state task parameters (dial_set_plan_params; nullptr elsewhere): row b into this workgroup's staged constants
+  if constexpr (D::user) {
+    if (plan_params) {
+      float* const up = const_cast<float*>(m->user_params);
+      w.items(DIAL_USER_PARAMS, [&](int k) { up[k] = plan_params[(size_t)b * DIAL_USER_PARAMS + k]; });
+    }
+  }
   dial::env_step_single(w, m, tg, s, state + (size_t)b * (nq + 2 * nv + DIAL_INFO_N), action + (size_t)b * nu,
                         xpos_out ? xpos_out + (size_t)b * nb1 * 3 : nullptr, xquat_out ? xquat_out + (size_t)b * nb1 * 4 : nullptr,
                         ctrl_out ? ctrl_out + (size_t)b * nu : nullptr);

@@ -208,9 +208,12 @@ class BaseEnv:
         ctx = self._context()
         return state.stepped(ctx, action)
 
-    def step_batch(self, states, actions):
-        """env.step of M states in one launch: a list of M States and actions [M, nu] -> a list of M new States."""
+    def step_batch(self, states, actions, user_params=None):
+        """env.step of M states in one launch: a list of M States and actions [M, nu] -> a list of M new States.
+        user_params: per-state task parameters -- a custom environment's (CustomEnv.step_batch); refused here."""
         import torch
+        if user_params is not None:
+            raise ValueError(f"{type(self).__name__}: per-state task parameters (user_params=) need a custom environment's task plugin")
         from dial_mpc_amd.envs.state import State
         ctx = self._context()
         packed = torch.stack([st.packed for st in states]).contiguous()

@@ -103,6 +103,40 @@ class CustomEnv(BaseEnv):
         if self._ctx is not None:
             self._ctx.set_user_params(self.user_param_vector())
 
+    def plan_params(self, **fields) -> np.ndarray:
+        """Per-plan task parameters: {name: [M values]} for names in user_params -> rows [M, len(user_params)], ordered as
+        user_params (what set_plan_params / step_batch / MBDPI.reverse_once_batch take).  A field not given keeps the config's
+        value in every row."""
+        if not fields:
+            raise ValueError("plan_params: give at least one field as a list of per-plan values")
+        cols = {}
+        for k, v in fields.items():
+            if k not in self.user_params:
+                raise KeyError(f"{k!r} is not one of {list(self.user_params)}")
+            cols[k] = np.atleast_1d(np.asarray(v, dtype=np.float64)).ravel()
+        lens = {k: len(v) for k, v in cols.items()}
+        M = next(iter(lens.values()))
+        if M < 1 or any(n != M for n in lens.values()):
+            raise ValueError(f"plan_params: every field needs the same number (>= 1) of per-plan values; got {lens}")
+        base = self.user_param_vector()
+        rows = np.tile(np.asarray(base, dtype=np.float32), (M, 1))
+        for j, name in enumerate(self.user_params):
+            if name in cols:
+                rows[:, j] = cols[name]
+        return rows
+
+    def step_batch(self, states, actions, user_params=None):
+        """env.step of M states in one launch; user_params: per-state task parameters [M, n] (plan_params), state g's reward
+        reads row g -- bound for this call only, the shared parameters apply again afterwards."""
+        if user_params is None:
+            return super().step_batch(states, actions)
+        ctx = self._context()
+        ctx.set_plan_params(user_params)
+        try:
+            return super().step_batch(states, actions)
+        finally:
+            ctx.set_plan_params(None)
+
     def _context(self):
         if self._ctx is None:
             from dial_mpc_amd import _lib

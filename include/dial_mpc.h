@@ -534,6 +534,17 @@ int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task*
 /* New task parameters for a plugin context (no rebuild): params:[n] host floats, n <= DIAL_USER_PARAMS, the rest zero.
  * Synchronises the device; launches issued afterwards see the new values. */
 int dial_set_user_params(dial_ctx* ctx, const float* params, int n);
+/* Per-plan task parameters of a task-plugin context.  params: [rows, DIAL_USER_PARAMS] float32 DEVICE memory, row g = the
+ * parameters of plan g (grouped launches) / state g (dial_env_step_batch); NULL = back to the shared parameters
+ * (dial_set_user_params).  The caller keeps the buffer alive while bound (like dial_set_state_trace).
+ * While bound, every launch of the context reads row g for plan / state g: dial_reverse_once_batch[_rng], dial_env_step_batch,
+ * and the single-plan entry points read row 0 (dial_reverse_once[_rng], dial_rollout, dial_env_step) -- a grouped launch of
+ * M = 1 stays the single-plan launch.  dial_env_reset[_batch] compute no reward.  dial_set_user_params still sets the shared
+ * vector, which applies again once the binding is cleared.  Fails with DIAL_ERR_ARG (dial_last_error names the reason) on a
+ * context without a task plugin or a sharded one, or rows outside 1 .. DIAL_MAX_PLANS with a non-NULL pointer; a grouped launch
+ * or batched env.step of M > rows plans / states fails with DIAL_ERR_ARG.  No synchronisation: launches issued afterwards see
+ * the binding. */
+int dial_set_plan_params(dial_ctx* ctx, const float* params, int rows);
 
 /* ABI self-description used by tests: sizeof of the three structs. */
 int dial_abi_sizes(int* model_bytes, int* task_bytes, int* cfg_bytes);

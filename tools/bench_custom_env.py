@@ -2,8 +2,10 @@
 """Custom environments: ms per reverse_once at Go2 N=2048 H=16 for (a) the example task plugin (go2_height_walk), (b) the Go2 walk
 task forced onto the capacity-dimension kernel (DimsMax, dial_options.force_generic), (c) the shipped DimsGo2 kernel; the plugin's
 cold compile time (empty cache) and its kernels' resource line (tools/isa/disasm_lib.py).  Writes a markdown report.
+--plan-params: instead, grouped reverse_once_batch_rng of the example plugin at M plans (--plans, default 4 and 32), the shared task
+parameters against bound per-plan rows (dial_set_plan_params), alternating.
 
-usage: bench_custom_env.py <out.md> [--iters 200] [--rounds 3]"""
+usage: bench_custom_env.py <out.md> [--iters 200] [--rounds 3] [--plan-params [--plans 4 32]]"""
 import argparse
 import importlib
 import os
@@ -39,11 +41,62 @@ def _ms_per_call(ctx, s0, dc, iters):
     return e0.elapsed_time(e1) / iters
 
 
+def _ms_per_batch(ctx, states, dc, iters, rows):
+    """ms per grouped reverse_once_batch_rng (lean) of len(states) plans; rows: per-plan parameters bound for the calls, or None."""
+    import torch
+    M = int(states.shape[0])
+    Ybar = torch.zeros((M, dc.Hnode + 1, ctx.nu), device="cuda")
+    sig = torch.full((M, dc.Hnode + 1), 0.3, device="cuda")
+    ctx.set_plan_params(rows)
+    for _ in range(10):
+        ctx.reverse_once_batch_rng(states, Ybar, sig, 0, 0, want_bars=False)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(iters):
+        ctx.reverse_once_batch_rng(states, Ybar, sig, 0, i, want_bars=False)
+    e1.record()
+    torch.cuda.synchronize()
+    ctx.set_plan_params(None)
+    ctx.status()
+    return e0.elapsed_time(e1) / iters
+
+
+def plan_params_report(a, env, dc, cfg):
+    import torch
+    from dial_mpc_amd import _lib
+    lines = ["# Per-plan task parameters: grouped plans of the example plugin, shared against bound rows", "",
+             f"reverse_once_batch_rng (lean: mean actions only), go2_height_walk plugin, N = {dc.Nsample}, H = {dc.Hsample}, "
+             f"Hnode = {dc.Hnode}; {a.iters} calls per measurement, {a.rounds} alternating rounds (median; all rounds listed).  "
+             "`shared`: every plan reads the context's one parameter vector; `rows`: dial_set_plan_params binds M rows (per-plan vx and "
+             "height), plan g's reward reads row g.", "",
+             "| M | parameters | ms per call (median) | ms per plan | rounds |", "|---|---|---|---|---|"]
+    for M in a.plans:
+        ctx = _lib.Context(env.make_model(), env.make_task(), cfg, options=dict(plan_cap=M), **env.context_kwargs())
+        q = torch.as_tensor(np.tile(env._init_q, (M, 1)), dtype=torch.float32, device="cuda")
+        states = ctx.env_reset_batch(q, torch.zeros((M, ctx.nv), device="cuda"))
+        rows = env.plan_params(vx=list(np.linspace(0.2, 1.2, M)), height=list(np.linspace(0.25, 0.35, M)))
+        res = {"shared": [], "rows": []}
+        for _ in range(a.rounds):   # alternating
+            res["shared"].append(_ms_per_batch(ctx, states, dc, a.iters, None))
+            res["rows"].append(_ms_per_batch(ctx, states, dc, a.iters, rows))
+        for k, v in res.items():
+            lines.append(f"| {M} | {k} | {np.median(v):.3f} | {np.median(v) / M:.4f} | {', '.join(f'{x:.3f}' for x in v)} |")
+        del ctx
+    isa = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa", "disasm_lib.py"), env.plugin_path(),
+                          os.path.join(tempfile.gettempdir(), "isa_plugin"), "--notes-only"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                         text=True).stdout.replace(ROOT + os.sep, "")   # (the plugin's path relative to the repository)
+    lines += ["", "Plugin kernels (tools/isa/disasm_lib.py --notes-only):", "", "```", isa.strip(), "```"]
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--plan-params", action="store_true", help="measure shared against per-plan task parameters instead")
+    ap.add_argument("--plans", type=int, nargs="+", default=[4, 32])
     a = ap.parse_args()
     import torch
     from dial_mpc_amd import _lib, plugin
@@ -52,6 +105,11 @@ def main():
     d = yaml.safe_load(open(os.path.join(ROOT, "dial_mpc_amd", "examples", "custom_env", "go2_height_walk.yaml")))
     d["Nsample"], d["Hsample"] = 2048, 16
     dc, _, env = load_dial_and_env(d)
+    if a.plan_params:
+        lines = plan_params_report(a, env, dc, make_cfg(dc))
+        open(a.out, "w").write("\n".join(lines) + "\n")
+        print("\n".join(lines))
+        return
     t = yaml.safe_load(open(os.path.join(ROOT, "dial_mpc_amd", "examples", "unitree_go2_trot.yaml")))
     t["Nsample"], t["Hsample"] = 2048, 16
     dct, _, go2 = load_dial_and_env(t)
