@@ -355,6 +355,9 @@ struct dial_ctx {
   int plan_cap = 1;            // plans of one grouped launch (dial_options.plan_cap): the rollout scratch holds plan_cap x B_cap rollouts
   float *Y0s = nullptr, *rewss = nullptr, *rews = nullptr, *qss = nullptr, *qdss = nullptr, *xss = nullptr;
   float *weights = nullptr, *partial = nullptr;
+  // Set while the last rollout launch left rows of the scratch above unwritten (a lean launch: DIAL_SHARD_LEAN, or a
+  // reverse_once[_batch] without bars), naming it; dial_shard_reduce* would sum stale rows and refuse to run.  A full launch clears it.
+  const char* rows_stale = nullptr;
   unsigned long long* prof = nullptr;
   size_t lds_bytes = 0;        // env_step / env_reset kernels (one wavefront, no node array)
   size_t lds_rollout = 0;      // rollout kernel: constants + DIAL_WPB workspaces
@@ -1129,6 +1132,7 @@ static int shard_rollout_impl(dial_ctx* ctx, const float* state, const float* Yb
   if (ns != 1 && ns != ctx->Hn1) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": noise_scale must have 1 or Hnode+1 entries");
   // with_mean: bit 0 = roll out the mean trajectory as an extra sample; bit 1 (DIAL_SHARD_LEAN) = the caller wants the mean action only
   // (dial_shard_ybar*): the rollouts do not materialise their per-step states nor their candidate nodes
+  if (with_mean & ~3) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": with_mean = " + std::to_string(with_mean) + " is outside 0 .. 3");
   if (with_mean & 2) store_states = false;
   const bool lean = (with_mean & 2) != 0;
   with_mean &= 1;
@@ -1139,7 +1143,11 @@ static int shard_rollout_impl(dial_ctx* ctx, const float* state, const float* Yb
                      lean ? nullptr : ctx->Y0s, ctx->rewss, rews_local, store_states ? ctx->qss : nullptr, store_states ? ctx->qdss : nullptr,
                      store_states ? ctx->xss : nullptr, ctx->prof,
                      use_rng, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), counter, n_begin};
-  return launch_rollout(ctx, io, B, (hipStream_t)stream);
+  if (lean) ctx->rows_stale = "the last rollout launch was lean (DIAL_SHARD_LEAN): it wrote neither the candidate nodes nor the per-step states";
+  else if (!store_states) ctx->rows_stale = "the last rollout launch formed the mean action only (reverse_once without bars): it wrote no per-step states";
+  const int rc = launch_rollout(ctx, io, B, (hipStream_t)stream);
+  if (rc == DIAL_OK && store_states) ctx->rows_stale = nullptr;
+  return rc;
 }
 
 int dial_shard_rollout(dial_ctx* ctx, const float* state, const float* Ybar_in, const float* noise_scale, int ns,
@@ -1201,6 +1209,8 @@ static int shard_reduce_impl(dial_ctx* ctx, const float* rews_all, const float* 
     return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": bad description of the gathered rewards");
   if (!ctx->has_cfg || n_local < 0 || n_local + 1 > ctx->B_cap || n_begin < 0 || n_begin + n_local > n_total)
     return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": bad shard description");
+  if (with_mean & ~3) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": with_mean = " + std::to_string(with_mean) + " is outside 0 .. 3");
+  if (ctx->rows_stale) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": the rollout rows it would sum are stale: " + ctx->rows_stale);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   // the global weights need n_total+1 floats of ctx->weights
@@ -1348,7 +1358,9 @@ static int reverse_once_batch_impl(dial_ctx* ctx, const float* states, const flo
                      bars ? ctx->xss : nullptr, ctx->prof, use_rng, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), counter, 0};
   io.plan_rollouts = N + 1;
   hipStream_t st = (hipStream_t)stream;
+  if (!bars) ctx->rows_stale = "the last rollout launch formed the mean action only (reverse_once_batch without bars): it wrote no per-step states";
   if (int rc = launch_rollout(ctx, io, B, st)) return rc;
+  if (bars) ctx->rows_stale = nullptr;
   hipLaunchKernelGGL(weights_kernel, dim3(M), dim3(WK_THREADS), 0, st, (const float*)rews, N + 1, ctx->hc.temp_sample, ctx->weights, (const float*)nullptr, 0, (float*)nullptr);
   HIP_TRY(ctx, hipGetLastError());
   return launch_wsum(ctx, ctx->weights, N + 1, 0, N, N, Ybar_out, qbar, qdbar, xbar, st, !bars, M);

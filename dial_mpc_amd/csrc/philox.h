@@ -28,7 +28,7 @@ DIAL_DEV void normal_quad(uint32_t n, uint32_t q, uint32_t it, uint32_t seed_lo,
   uint32_t u[4];
   philox4x32_10(n, q, it, 0u, seed_lo, seed_hi, u);
   for (int h = 0; h < 2; h++) {
-    const float u1 = ((float)(u[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0, 1)
+    const float u1 = ((float)(u[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0, 1]: the top value rounds to 2^24, u1 = 1, z = 0
     const float u2 = ((float)(u[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
 #ifdef DIAL_EMU
     const float r = std::sqrt(-2.0f * std::log(u1));

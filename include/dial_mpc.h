@@ -416,6 +416,9 @@ int dial_reverse_once(dial_ctx* ctx, const float* state, const float* Ybar_in,
 int dial_shard_rollout(dial_ctx* ctx, const float* state, const float* Ybar_in,
                        const float* noise_scale, int ns, const float* eps, int n_local,
                        int with_mean, float* rews_local, void* stream);
+/* dial_shard_reduce* sum the rows the last rollout launch of the context wrote: after a lean launch (DIAL_SHARD_LEAN, or a
+ * dial_reverse_once[_batch] without bars) they fail with DIAL_ERR_ARG until a full launch has written the rows again.  with_mean
+ * outside 0 .. 3 fails with DIAL_ERR_ARG here and in dial_shard_rollout*.                                                      */
 int dial_shard_reduce(dial_ctx* ctx, const float* rews_all, int n_total, int n_begin,
                       int n_local, int with_mean, float* packed_out, void* stream);
 /* Single-collective variant (SURVEY 8e option (a)): after the all-gather of the rewards every rank forms the

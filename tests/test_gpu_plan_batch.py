@@ -55,16 +55,23 @@ def test_batch_equals_single_plans_bit_for_bit(example, H):
         assert (out["qbar"] is None) == (not want_bars)
 
 
-@pytest.mark.parametrize("example,H", [("unitree_go2_trot", 8), ("allegro_reorient", 8)])
+@pytest.mark.parametrize("example,H", [("unitree_go2_trot", 8), ("unitree_h1_jog", 16), ("allegro_reorient", 8)])
 def test_in_kernel_noise_is_rng_fill_of_the_global_sample_index(example, H):
+    """(H1: C = 114 elements per sample, the last Philox quad is cut after two.)  The candidate nodes the rollouts drew are
+    clip(rng_fill sigma + Ybar) with node 0 held at clip(Ybar[0]), the mean row clip(Ybar), plan by plan."""
     import torch
+    import planner_ref as R
     from dial_mpc_amd import _lib
     N, M, seed, counter = 64, 3, 4242, 7
     dc, env, model, task, cfg = setup_case(example, N, H)
     ctx = _lib.Context(model, task, cfg, options=dict(plan_cap=M))
     states, Ybars, scales, _ = _plans(ctx, env, dc, model, M, seed=3)
     got = {k: v.clone() if v is not None else None for k, v in ctx.reverse_once_batch_rng(states, Ybars, scales, seed, counter).items()}
+    nodes = R.download(ctx, "Y0s", M * (N + 1)).reshape(M, N + 1, -1)
     eps = ctx.rng_fill(seed, counter, 0, M * N).reshape(M, N, dc.Hnode + 1, model.nu).contiguous()
+    for g in range(M):
+        want, mag, _ = R.candidate_nodes(eps[g].cpu().numpy().reshape(N, -1), Ybars[g].cpu().numpy(), scales[g].cpu().numpy(), model.nu)
+        assert np.all(np.abs(nodes[g] - want) <= 2 * R.U * mag), g      # (one fp32 multiply-add, or a multiply and an add)
     ref = ctx.reverse_once_batch(states, Ybars, scales, eps)
     for k in ("rews",) + BARS:
         assert torch.equal(got[k], ref[k]), k

@@ -5,7 +5,7 @@ The synchronous driver loop of dial_core.py:245-266 (env.step, shift, Ndiffuse a
 
   --mode gpu     the product: HIP plant + HIP planner (MBDPI with the in-kernel Philox noise), many seeds, any N      [needs a GPU]
   --mode oracle  the CPU checker as plant AND as the planner's rollout engine (fp32 oracle, oracle/dial_oracle.c), fed with the
-                 SAME noise: Philox4x32-10 + Box-Muller restated in NumPy below (csrc/philox.h; the device's approximate log /
+                 SAME noise: Philox4x32-10 + Box-Muller restated in NumPy (tests/philox_ref.py, csrc/philox.h; the device's approximate log /
                  sin / cos differ from NumPy's in the last bits: the draws agree to ~1e-6), same seed / call counter sequence.
 
 Both print one line per seed (ball height at ticks 10 / 20 / ... and whether it left the hand) and a summary.  If the oracle-driven
@@ -27,37 +27,11 @@ import yaml
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from dial_mpc_amd.core.dial_core import load_dial_and_env, make_cfg  # noqa: E402
 from dial_mpc_amd.utils.io_utils import get_example_path  # noqa: E402
-
-
-def philox_normal(seed, counter, n_count, C):
-    """csrc/philox.h + rng_fill_kernel in NumPy: eps[n, c], n < n_count, c < C (= (Hnode + 1) * nu), counter = annealing-call index."""
-    nq = (C + 3) // 4
-    n = np.repeat(np.arange(n_count, dtype=np.uint32), nq)
-    q = np.tile(np.arange(nq, dtype=np.uint32), n_count)
-    c0, c1, c2, c3 = n.copy(), q.copy(), np.full_like(n, counter), np.zeros_like(n)
-    k0, k1 = np.uint32(seed & 0xffffffff), np.uint32((seed >> 32) & 0xffffffff)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c0.astype(np.uint64)
-        p1 = np.uint64(0xCD9E8D57) * c2.astype(np.uint64)
-        n0 = (p1 >> np.uint64(32)).astype(np.uint32) ^ c1 ^ k0
-        n1 = p1.astype(np.uint32)
-        n2 = (p0 >> np.uint64(32)).astype(np.uint32) ^ c3 ^ k1
-        n3 = p0.astype(np.uint32)
-        c0, c1, c2, c3 = n0, n1, n2, n3
-        k0 = np.uint32((int(k0) + 0x9E3779B9) & 0xffffffff)
-        k1 = np.uint32((int(k1) + 0xBB67AE85) & 0xffffffff)
-    u = [c0, c1, c2, c3]
-    z = np.empty((n.size, 4), np.float32)
-    for h in range(2):
-        u1 = ((u[2 * h] >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
-        u2 = ((u[2 * h + 1] >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
-        r = np.sqrt(np.float32(-2.0) * np.log(u1)).astype(np.float32)
-        z[:, 2 * h] = r * np.cos(np.float32(6.283185307179586) * u2)
-        z[:, 2 * h + 1] = r * np.sin(np.float32(6.283185307179586) * u2)
-    return z.reshape(n_count, nq * 4)[:, :C]
+from philox_ref import philox_normal  # noqa: E402,F401  (the one NumPy restatement of csrc/philox.h; tools import it from here)
 
 
 def setup(nsample, seed):

@@ -57,7 +57,8 @@ def analyse(path, nsample):
     the plan the update settled on predicts for the ball (oracle rollout of it) against what the plant then did; (4) the ORACLE's loop (oracle
     plant + oracle planner, same Philox noise) continued from the recorded state four ticks before the toss."""
     import oracle as O
-    from allegro_closed_loop_study import philox_normal, setup
+    from allegro_closed_loop_study import setup
+    from philox_ref import philox_normal
     from dial_mpc_amd.core.dial_core import make_cfg
     seed = int(os.path.basename(path).replace("seed", "").replace(".npz", ""))
     dc, ec, env = setup(nsample, seed)

@@ -36,7 +36,8 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from allegro_closed_loop_study import philox_normal, setup  # noqa: E402
+from allegro_closed_loop_study import setup  # noqa: E402
+from philox_ref import philox_normal  # noqa: E402
 from dial_mpc_amd.core.dial_core import make_cfg  # noqa: E402
 
 VARIANTS = {"emu[off]": ((), ""), "emu[fma]": (("-march=native", "-ffp-contract=fast"), "_fma"),
