@@ -46,7 +46,8 @@ _FAST = ["-DDIAL_FUSED_DPP", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-Xa
 # rounded on its own, as the CPU oracle computes.  Which a * b + c pairs the compiler fuses depends on the basic-block structure around
 # them, i.e. differs between two kernels that run the same arithmetic on different lane layouts: this variant is where the Go2's
 # two-samples-per-wavefront kernel is compared BIT FOR BIT with the one-sample kernel (tests/test_gpu_parity.py).
-_IEEE = ["-Xarch_device", "-ffp-contract=off"]
+# (-DDIAL_IEEE_BUILD, host code only: this variant carries no plant simulator -- dial_plant_step fails with DIAL_ERR_UNSUPPORTED)
+_IEEE = ["-Xarch_device", "-ffp-contract=off", "-DDIAL_IEEE_BUILD"]
 _COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Xarch_device", "-fno-slp-vectorize"]
 # per robot family (kern_family.hip -DDIAL_FAMILY=k): LLVM's "max-ilp" machine-scheduling strategy for the Allegro's kernels -- their
 # launch lasts as long as ONE lone wavefront's dependence chain, which the strategy shortens: A/B on one box
@@ -70,10 +71,29 @@ def build(force: bool = False, verbose: bool = False, ieee: bool = False) -> str
     multiply-add contraction (_IEEE above).  It is never the product
     path; the GPU suite loads it next to the product library to show how much of the knife-edge witness traffic is the
     fast-math rounding (tests/test_gpu_parity.py: test_ieee_build_needs_no_more_witnesses)."""
+    if not ieee:   # the plant simulator's kernels: a library of their own next to the product library (build_plant)
+        build_plant(force=force, verbose=verbose)
+    return _build_lib(IEEE_LIB_PATH if ieee else LIB_PATH, [(os.path.join(_CSRC, "dial_hip.hip"), [], "dial_hip.o")] +
+                      [(os.path.join(_CSRC, "kern_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []), f"kern_family_{k}.o")
+                       for k in range(N_FAMILIES)], force, verbose, ieee)
+
+
+PLANT_LIB_PATH = os.path.join(_CSRC, "libdialplant.so")
+N_PLANT_FAMILIES = 7   # kernel_list.h's families 0 .. 6 (7, the Go2's pair kernels, has no env.step and no plant)
+
+
+def build_plant(force: bool = False, verbose: bool = False) -> str:
+    """libdialplant.so: the plant kernel (csrc/plant_kernel.h) once per robot family (plant_family.hip -DDIAL_FAMILY=k, the product
+    flags and _FAMILY_FLAGS), kept out of libdialhip.so so that its code objects stay as shipped.  libdialhip.so's dial_plant_step
+    loads it from its own directory on first use.  Same staleness check, lock and parallel compile as `build`."""
+    return _build_lib(PLANT_LIB_PATH, [(os.path.join(_CSRC, "plant_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []),
+                                        f"plant_family_{k}.o") for k in range(N_PLANT_FAMILIES)], force, verbose, False)
+
+
+def _build_lib(out: str, units, force: bool, verbose: bool, ieee: bool) -> str:
     from concurrent.futures import ThreadPoolExecutor
     # every source of the library takes part in the staleness check (a stale .so must never ship silently)
     srcs = sorted(glob.glob(os.path.join(_CSRC, "*.h")) + glob.glob(os.path.join(_CSRC, "*.hip"))) + [_abi.HEADER, os.path.abspath(__file__)]   # (this file: the flags)
-    out = IEEE_LIB_PATH if ieee else LIB_PATH
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
         return out
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -96,9 +116,7 @@ def build(force: bool = False, verbose: bool = False, ieee: bool = False) -> str
             if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
                 return out
             os.makedirs(objdir, exist_ok=True)
-            units = [(os.path.join(_CSRC, "dial_hip.hip"), [], os.path.join(objdir, "dial_hip.o"))]
-            units += [(os.path.join(_CSRC, "kern_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []), os.path.join(objdir, f"kern_family_{k}.o"))
-                      for k in range(N_FAMILIES)]
+            units = [(src, defs, os.path.join(objdir, obj)) for src, defs, obj in units]
 
             def compile_unit(u):
                 src, defs, obj = u
@@ -109,7 +127,7 @@ def build(force: bool = False, verbose: bool = False, ieee: bool = False) -> str
                 if r.returncode != 0:   # (the compiler's own words, not just the exit status: a failed unit must be impossible to overlook)
                     raise DialHipError(f"hipcc failed ({r.returncode}) on {os.path.basename(src)} {' '.join(defs)}:\n{r.stdout[-4000:]}")
                 return obj
-            with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1)) as pool:
+            with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1, 16)) as pool:
                 objs = list(pool.map(compile_unit, units))
             cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp_out] + objs
             if verbose:
@@ -182,6 +200,11 @@ def load(path: Optional[str] = None):
     except AttributeError:
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack per-plan task parameters)
             raise
+    try:
+        lib.dial_plant_step.argtypes = [vp, fp, fp, fp, fp, ci, ctypes.c_double, ctypes.c_double, ci, ci, fp, ci, vp]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack the plant simulator)
+            raise
     lib.dial_env_reset.argtypes = [vp, fp, fp, fp, fp, fp, vp]
     lib.dial_env_reset_batch.argtypes = [vp, fp, fp, fp, fp, fp, ci, vp]
     lib.dial_status.argtypes = [vp]
@@ -203,7 +226,10 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
             "dial_shard_ybar_gathered", "dial_shard_ybar_gathered_rng", "dial_shard_reduce_gathered", "dial_shift", "dial_env_step", "dial_env_reset", "dial_env_reset_batch",
             "dial_status", "dial_set_timing", "dial_get_rollout_ms", "dial_abi_sizes",
             "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch",
-            "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params")
+            "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params", "dial_plant_step")
+
+# dial_plant_step flags (include/dial_mpc.h)
+PLANT_CTRL, PLANT_PD, PLANT_HOLD_FIRST = (_abi.MACROS[k] for k in ("DIAL_PLANT_CTRL", "DIAL_PLANT_PD", "DIAL_PLANT_HOLD_FIRST"))
 
 
 def plan_param_rows(rows) -> np.ndarray:
@@ -371,6 +397,23 @@ class Context:
         self._check(self.lib.dial_env_step(self.h, _ptr(state), _ptr(action), _ptr(xpos), _ptr(xquat), _ptr(ctrl),
                                            _stream()), "dial_env_step")
         return state, xpos, xquat, ctrl
+
+    # ---- plant simulator (dial_plant_step; deploy/plant.py)
+    def plant_step(self, states, t, plan_time, ctrl, ctrl_dt: float, sim_dt: float, K: int, flags: int, trace=None):
+        """K physics steps of M plants in one launch, all in place: states [M, state_size] float32, t [M] float64 clocks,
+        plan_time [M] float32, ctrl [M, T, nu] float32 (the published rows), trace [M, K, 1 + nq + nv + nu] float32 or None.
+        The context's model must have timestep = sim_dt (Plant / env.make_plant build one)."""
+        import torch
+        M = int(states.shape[0])
+        assert states.dim() == 2 and states.shape[1] == self.state_size, "states: [M, state_size]"
+        assert ctrl.dim() == 3 and ctrl.shape[0] == M and ctrl.shape[2] == self.nu, "ctrl: [M, T, nu]"
+        assert tuple(t.shape) == (M,) and t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), "t: [M] float64 device tensor"
+        assert tuple(plan_time.shape) == (M,), "plan_time: [M]"
+        if trace is not None:
+            assert tuple(trace.shape) == (M, int(K), 1 + self.nq + self.nv + self.nu), "trace: [M, K, 1 + nq + nv + nu]"
+        self._check(self.lib.dial_plant_step(self.h, _ptr(states), t.data_ptr(), _ptr(plan_time), _ptr(ctrl), int(ctrl.shape[1]),
+                                             float(ctrl_dt), float(sim_dt), int(K), int(flags), _ptr(trace), M, _stream()),
+                    "dial_plant_step")
 
     # ---- K3
     def rollout(self, state, us, want_states: bool = True):

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "kernel_list.h"
+#include "plant_kernel.h"
 #include "plugin_ops.h"
 
 // the kernels are compiled in their own translation units, one per robot family (kern_family.hip, built in parallel)
@@ -1454,6 +1455,85 @@ int dial_env_reset(dial_ctx* ctx, const float* qpos, const float* qvel, float* s
 int dial_env_reset_batch(dial_ctx* ctx, const float* qpos, const float* qvel, float* states, float* xpos_out,
                          float* xquat_out, int n, void* stream) {
   return env_reset_launch(ctx, qpos, qvel, states, xpos_out, xquat_out, n, stream, "dial_env_reset_batch: null argument or n < 1");
+}
+
+// ------------------------------------------------------------------ plant simulator (dial_plant_step)
+// The plant kernels live in libdialplant.so (plant_family.hip), next to this library, so that this library's code objects stay as
+// shipped; its table (plant_kernel.h: dial_plant_ops) is looked up on first use and kept for the process, like a task plugin's.
+#ifndef DIAL_IEEE_BUILD
+struct PlantLib {
+  const dial_plant_ops* ops = nullptr;
+  std::string err;
+};
+static PlantLib plant_load() {
+  PlantLib r;
+  Dl_info info{};
+  std::string dir = ".";
+  if (dladdr((const void*)&plant_load, &info) && info.dli_fname) {
+    dir = info.dli_fname;
+    const size_t slash = dir.rfind('/');
+    dir = slash == std::string::npos ? "." : dir.substr(0, slash);
+  }
+  const std::string path = dir + "/libdialplant.so";
+  void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);   // (never dlclose'd: the runtime holds its code objects)
+  if (!h) { r.err = "dial_plant_step: cannot load " + path + " (build it: dial_mpc_amd._lib.build()): " + dlerror(); return r; }
+  dial_plant_entry entry = (dial_plant_entry)dlsym(h, DIAL_PLANT_SYMBOL);
+  const dial_plant_ops* o = entry ? entry() : nullptr;
+  if (!o) r.err = "dial_plant_step: " + path + " does not export " DIAL_PLANT_SYMBOL;
+  else if (o->abi_version != DIAL_PLANT_ABI_VERSION || o->sizeof_model != sizeof(dial_model) || o->sizeof_task != sizeof(dial_task))
+    r.err = "dial_plant_step: " + path + " was built against another version of the library (rebuild it)";
+  else r.ops = o;
+  return r;
+}
+static const PlantLib& plant_lib() {
+  static const PlantLib lib = plant_load();   // (once per process, thread-safe initialisation)
+  return lib;
+}
+
+static size_t cmodel_bytes_of(int inst) {
+  switch (inst) {
+    case 1: return sizeof(CModel<DimsGo2>);
+    case 2: return sizeof(CModel<DimsH1>);
+    case 3: return sizeof(CModel<DimsH1Loco>);
+    case 4: return sizeof(CModel<DimsAllegro>);
+    case 5: return sizeof(CModel<DimsGo2Crate>);
+    case 6: return sizeof(CModel<DimsH1PushCrate>);
+    default: return sizeof(CModel<DimsMax>);
+  }
+}
+#endif
+
+int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_time, const float* ctrl, int T, double ctrl_dt,
+                    double sim_dt, int K, int flags, float* trace, int M, void* stream) {
+  if (!ctx) return fail(nullptr, DIAL_ERR_ARG, "dial_plant_step: null context");
+  if (!states || !t || !plan_time || !ctrl) return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: null argument (states, t, plan_time and ctrl are required)");
+  if (K < 1 || T < 1 || M < 1) return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: K, T and M must be >= 1");
+  if (M > DIAL_MAX_PLANTS) return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: M exceeds DIAL_MAX_PLANTS");
+  const int mode = flags & (DIAL_PLANT_CTRL | DIAL_PLANT_PD);
+  if ((flags & ~(DIAL_PLANT_CTRL | DIAL_PLANT_PD | DIAL_PLANT_HOLD_FIRST)) != 0 || (mode != DIAL_PLANT_CTRL && mode != DIAL_PLANT_PD))
+    return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: flags must hold exactly one of DIAL_PLANT_CTRL / DIAL_PLANT_PD, optionally DIAL_PLANT_HOLD_FIRST");
+  if (mode == DIAL_PLANT_PD)
+    for (int a = 0; a < ctx->hm.nu; a++)
+      if (ctx->hm.act_isposition[a])
+        return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: DIAL_PLANT_PD on a model with position actuators (use DIAL_PLANT_CTRL: the row is their target)");
+  if (!(ctrl_dt > 0.0) || !(sim_dt > 0.0)) return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: ctrl_dt and sim_dt must be > 0");
+  if ((float)sim_dt != ctx->hm.timestep)
+    return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: sim_dt differs from the model's timestep (create the context with timestep = sim_dt)");
+  if (ctx->plug) return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: task-plugin contexts have no plant (custom environments are not simulated)");
+#ifdef DIAL_IEEE_BUILD
+  (void)trace; (void)stream;
+  return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: the IEEE measurement build carries no plant (use the product library)");
+#else
+  const dial_plant_ops* ops = plant_lib().ops;
+  if (!ops) return fail(ctx, DIAL_ERR_UNSUPPORTED, plant_lib().err);
+  if (ctx->inst < 0 || ctx->inst >= DIAL_PLANT_INSTS || ops->cmodel_bytes[ctx->inst] != cmodel_bytes_of(ctx->inst))
+    return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: libdialplant.so does not match this library's constants (rebuild both)");
+  if (int rc = check_sticky(ctx)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ops->launch[ctx->inst](ctx->dcm, ctx->lds_bytes, (hipStream_t)stream, states, t, plan_time, ctrl, T, ctrl_dt, sim_dt, K, flags,
+                                      trace, M));
+  return DIAL_OK;
+#endif
 }
 
 // Internal diagnostics (not part of the public header): wave primitive self-test and the scratch

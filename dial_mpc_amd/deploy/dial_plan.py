@@ -11,8 +11,9 @@ re-evaluated at step_nodes + shift_time (:136-139, right-side extrapolation as F
 ``reverse_once`` iterations with the ASYNC noise schedule traj_diffuse_factor**i (no sigma_control, :207-209)
 -> publish joint targets, torques, plan time and body-position references.
 
-The plant side (native-MuJoCo simulator, Unitree DDS bridge) is out of scope; the tests drive this module with a
-test double that owns the segments and steps the same HIP env (``tests/fake_plant.py``).
+The plant side is ``dial-mpc-sim`` (deploy/dial_sim.py: the env's own scene on the HIP path, ``dial-mpc-sim2sim`` starts
+both); the Unitree DDS bridge is out of scope.  The tests also drive this module with a test double that owns the segments and
+steps the same HIP env once per tick (``tests/fake_plant.py``).
 """
 from __future__ import annotations
 
@@ -192,6 +193,8 @@ def main(args=None):
     group.add_argument("--example", type=str, default=None, help="Example to run")
     group.add_argument("--list-examples", action="store_true", help="List available examples")
     parser.add_argument("--custom-env", type=str, default=None, help="Custom environment to import dynamically")
+    parser.add_argument("--shm-prefix", type=str, default="", help="Prefix of the shared-memory segment names (the plant's)")
+    parser.add_argument("--max-ticks", type=int, default=None, help="Stop after this many plans (default: run until interrupted)")
     args = parser.parse_args(args)
     if args.custom_env is not None:
         sys.path.append(os.getcwd())
@@ -210,9 +213,9 @@ def main(args=None):
         config_dict = yaml.safe_load(open(args.config, "r"))
     print("Creating environment")
     dial_config, env_config, env = load_dial_and_env(config_dict)
-    pub = MBDPublisher(env, env_config, dial_config)
+    pub = MBDPublisher(env, env_config, dial_config, shm_prefix=args.shm_prefix)
     try:
-        pub.main_loop()
+        pub.main_loop(max_ticks=args.max_ticks)
     except KeyboardInterrupt:
         pass
     finally:

@@ -186,6 +186,19 @@ class BaseEnv:
     def make_model(self) -> "_abi.DialModel":
         return _abi.make_model(self.sys.model)
 
+    def make_plant(self, sim_dt: float, device: Optional[int] = None):
+        """The context of the plant simulator (deploy/plant.py, dial_plant_step): this env's compiled scene with timestep = sim_dt,
+        and its task with one physics step per step (n_frames = 1, dt = sim_dt).  Nothing else of the physics changes."""
+        from dial_mpc_amd import _lib
+        model = self.make_model()
+        model.timestep = float(sim_dt)
+        task = self.make_task()
+        task.n_frames, task.dt = 1, float(sim_dt)
+        return _lib.Context(model, task, None, self._device_or(device))
+
+    def _device_or(self, device):
+        return device if device is not None else getattr(self, "_device", None)
+
     # ---- HIP-backed reset / step (device tensors in, device tensors out)
     def bind_device(self, device: Optional[int]):
         """Run env.reset / env.step on this GPU (MBDPI binds the env to its own device)."""

@@ -62,6 +62,12 @@ extern "C" {
 #define DIAL_INFO_N 48     /* floats of env info in the packed state             */
 #define DIAL_MAX_CMD 16    /* randomize_tasks: velocity commands of the episodes step / 500 = 0, 1, ... (wraps)  */
 #define DIAL_MAX_PLANS 1024 /* dial_options.plan_cap: plans of one grouped launch (dial_reverse_once_batch)    */
+#define DIAL_MAX_PLANTS 65536 /* dial_plant_step: plants of one launch                                          */
+
+/* dial_plant_step flags: exactly one of CTRL / PD, optionally HOLD_FIRST */
+#define DIAL_PLANT_CTRL 1        /* the control row is the actuators' ctrl as it is (MuJoCo's data.ctrl = row)          */
+#define DIAL_PLANT_PD 2          /* the control row is a joint target: ctrl = clip(kp (q* - q) - kd qd, tau_range) per step */
+#define DIAL_PLANT_HOLD_FIRST 4  /* every step applies row 0 (sync mode); otherwise the row follows the clock               */
 
 /* joint types (MuJoCo numbering) */
 #define DIAL_JNT_FREE 0
@@ -548,6 +554,26 @@ int dial_set_user_params(dial_ctx* ctx, const float* params, int n);
  * or batched env.step of M > rows plans / states fails with DIAL_ERR_ARG.  No synchronisation: launches issued afterwards see
  * the binding. */
 int dial_set_plan_params(dial_ctx* ctx, const float* params, int rows);
+
+/* Plant simulator (deploy/dial_sim.py): M plants advanced by K physics steps in ONE launch, each step applying one row of the plan
+ * the planner published -- what the reference's dial_sim.py does with MuJoCo's mj_step at sim_dt.  The context is an ordinary
+ * dial_create context (cfg may be NULL) whose model has timestep = sim_dt and whose task has n_frames = 1 and dt = sim_dt; the
+ * physics is the env.step's own (forward + euler), without the task's action mapping, reward or info update.
+ *   states:[M,nstate] packed states (qpos | qvel | qacc_warmstart | info) in place; the info is left untouched.
+ *   t:[M] fp64 clocks, advanced in place by t += sim_dt per step.  plan_time:[M] float32 (the planner's plan_time_shm).
+ *   ctrl:[M,T,nu] the published rows (tau_shm or acts_shm).
+ * Row of a step (without DIAL_PLANT_HOLD_FIRST), in fp64: delta = t - plan_time, k = (int)(delta / ctrl_dt) truncated toward
+ * zero, and k = T - 1 when k >= T or k < 0 (dial_sim.py's rule).  DIAL_PLANT_HOLD_FIRST: row 0 (sync mode).
+ * DIAL_PLANT_CTRL: ctrl = row, applied by the model's actuators (ctrlrange clip where limited, motor or position actuators).
+ * DIAL_PLANT_PD: ctrl = clip(kp (row - q) - kd qd, tau_range) at every step, kp / kd / tau_range of the task (act2tau without
+ * act2joint); refused on models with position actuators.
+ *   trace:[M,K,1+nq+nv+nu] or NULL: per step, BEFORE it, [(float)t, qpos, qvel, ctrl applied] (dial_sim.py's record row).
+ * Every pointer is device memory.  The kernels live in libdialplant.so next to this library (loaded on first use).
+ * Fails with DIAL_ERR_ARG and a message on null pointers, K / T / M < 1, M > DIAL_MAX_PLANTS, unknown flags, DIAL_PLANT_PD on a
+ * model with position actuators, or (float)sim_dt != the model's timestep; with DIAL_ERR_UNSUPPORTED on task-plugin contexts, when
+ * libdialplant.so is missing, and in the IEEE measurement build. */
+int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_time, const float* ctrl, int T, double ctrl_dt,
+                    double sim_dt, int K, int flags, float* trace, int M, void* stream);
 
 /* ABI self-description used by tests: sizeof of the three structs. */
 int dial_abi_sizes(int* model_bytes, int* task_bytes, int* cfg_bytes);

@@ -10,5 +10,7 @@ setup(
     package_data={"dial_mpc_amd": ["models/*/*.json", "examples/*.yaml", "examples/custom_env/*", "csrc/*", "../include/*.h"]},
     install_requires=["numpy", "pyyaml", "torch"],
     entry_points={"console_scripts": ["dial-mpc=dial_mpc_amd.core.dial_core:main",
-                                      "dial-mpc-plan=dial_mpc_amd.deploy.dial_plan:main"]},
+                                      "dial-mpc-plan=dial_mpc_amd.deploy.dial_plan:main",
+                                      "dial-mpc-sim=dial_mpc_amd.deploy.dial_sim:main",
+                                      "dial-mpc-sim2sim=dial_mpc_amd.core.dial_sim2sim:main"]},
 )
