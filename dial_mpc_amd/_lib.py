@@ -215,6 +215,11 @@ def load(path: Optional[str] = None):
     lib.dial_debug_scratch.argtypes = [vp] + [ctypes.POINTER(vp)] * 6
     lib.dial_lds_bytes.argtypes = [vp]
     lib.dial_debug_resident_rollouts.argtypes = [vp, ctypes.c_int]
+    try:
+        lib.dial_debug_last_launch.argtypes = [vp, ctypes.POINTER(ci), ci]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack the launch record)
+            raise
     if path is None:
         _lib = lib
     return lib
@@ -589,6 +594,20 @@ class Context:
         self._trace = torch.zeros((int(rows), self.cfg.Hsample + 1, self.state_size), dtype=torch.float32, device=self.torch_device)
         self._check(self.lib.dial_set_state_trace(self.h, _ptr(self._trace), int(rows)), "dial_set_state_trace")
         return self._trace
+
+    LAUNCH_FIELDS = ("inst", "wpb", "blocks", "queue", "relay", "mean_inline", "slice_pieces", "split", "pair", "trace", "con_cap", "rollouts")
+
+    def debug_last_launch(self) -> dict:
+        """What this context's most recent rollout launch did (dial_debug_last_launch; tests assert the path they target): kernel
+        instantiation `inst` (0 = the capacity-dimension kernel, DimsMax), wavefronts per workgroup, grid workgroups (0: the call returned
+        before launching), and 0 / 1 or counts for the rollout queue, the mean-trajectory relay, the interleaved mean trajectory, the
+        time-slice pieces, the split launch, the Go2 pair kernel, the state-trace instantiation; `con_cap` the overflow cap in effect
+        (0: no overflow areas), `rollouts` the batch."""
+        buf = (ctypes.c_int * len(self.LAUNCH_FIELDS))()
+        n = self.lib.dial_debug_last_launch(self.h, buf, len(buf))
+        if n != len(self.LAUNCH_FIELDS):
+            raise DialHipError(f"dial_debug_last_launch: {n} fields, this wrapper knows {len(self.LAUNCH_FIELDS)}")
+        return dict(zip(self.LAUNCH_FIELDS, buf))
 
     def debug_scratch(self):
         """Host copies of the scratch tensors of the last reverse_once (tests only)."""

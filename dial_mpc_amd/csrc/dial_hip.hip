@@ -334,6 +334,10 @@ extern "C" __global__ void __launch_bounds__(64) selftest_kernel(float* out) {
 }
 
 // ------------------------------------------------------------------ host side
+// dial_debug_last_launch: what the context's most recent rollout launch did, one int per field (tests assert the path they target)
+enum LaunchField { LF_INST, LF_WPB, LF_BLOCKS, LF_QUEUE, LF_RELAY, LF_MEAN_INLINE, LF_SLICE_PIECES, LF_SPLIT, LF_PAIR, LF_TRACE, LF_CON_CAP,
+                   LF_ROLLOUTS, DIAL_LAUNCH_FIELDS };
+
 struct dial_ctx {
   int device = 0;
   dial_model hm;
@@ -396,6 +400,7 @@ struct dial_ctx {
   float* trace = nullptr;      // diagnostics: per-step packed states of the rollouts (dial_set_state_trace), caller-owned
   int trace_rows = 0;
   int ovf_slots = 0;           // overflow areas allocated (>= the largest grid this context ever launches)
+  int last_launch[DIAL_LAUNCH_FIELDS] = {};   // diagnostics: shape of the last rollout launch (dial_debug_last_launch)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
   std::string err;
@@ -698,9 +703,11 @@ static int create_impl(dial_ctx** out, const dial_model* model, const dial_task*
     else if (own && dims_match<DimsH1>(model) && derived_fits<DimsH1>(&ctx->hd) && kind_ok(dial::task_kind_mask<DimsH1>())) { ctx->inst = 2; ctx->wpb = 3; urc = upload(DimsH1{}); }
     else if (own && dims_match<DimsH1Loco>(model) && derived_fits<DimsH1Loco>(&ctx->hd) && kind_ok(dial::task_kind_mask<DimsH1Loco>())) { ctx->inst = 3; ctx->wpb = 2; urc = upload(DimsH1Loco{}); }
     else if (model->cone == DIAL_CONE_ELLIPTIC) {
-      if (!(kbi_ok && dims_match<DimsAllegro>(model) && ell_fits<DimsAllegro>(model, &ctx->hd))) {
+      // (options.force_generic included: the capacity-dimension kernel has no elliptic-cone solver)
+      if (opt.force_generic || !(kbi_ok && dims_match<DimsAllegro>(model) && ell_fits<DimsAllegro>(model, &ctx->hd))) {
         dial_destroy(ctx);
-        return fail(nullptr, DIAL_ERR_UNSUPPORTED, "dial_create: elliptic-cone models need a dimension-specialised instantiation (built: Allegro hand)");
+        return fail(nullptr, DIAL_ERR_UNSUPPORTED, std::string("dial_create: elliptic-cone models need a dimension-specialised instantiation (built: Allegro hand)") +
+                                                   (opt.force_generic ? "; options.force_generic does not apply to them" : ""));
       }
       ctx->inst = 4; ctx->wpb = DIAL_ALLEGRO_WPB; urc = upload(DimsAllegro{});
     }
@@ -709,6 +716,7 @@ static int create_impl(dial_ctx** out, const dial_model* model, const dial_task*
     else if (own && opt.con_cap >= 0 && dims_match<DimsH1PushCrate>(model) && kind_ok(dial::task_kind_mask<DimsH1PushCrate>())) { ctx->inst = 6; ctx->wpb = DIAL_CRATE_WPB; urc = upload(DimsH1PushCrate{}); }
     else { ctx->inst = 0; ctx->wpb = 1; urc = upload(DimsMax{}); }
     if (urc != DIAL_OK) { dial_destroy(ctx); return fail(nullptr, urc, "dial_create: uploading the model constants failed"); }
+    ctx->last_launch[LF_INST] = ctx->inst;   // (dial_debug_last_launch before any rollout launch: the instantiation, blocks = 0)
   }
   if (!cfg) ctx->lds_rollout = ctx->lds_bytes;   // no cfg: env.step / env.reset only -- no rollout launch, no capped workspace to size
   if (ctx->lds_rollout > 160 * 1024 || ctx->lds_bytes > 64 * 1024) {
@@ -924,6 +932,11 @@ int dial_get_rollout_ms(dial_ctx* ctx, double* total_ms, int* launches) {
 
 static bool opt_no_queue(const dial_ctx* ctx) { return ctx->opt.no_queue != 0; }
 static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hipStream_t st) {
+  // the launch record (dial_debug_last_launch): reset first, so that a call that returns before launching leaves blocks = 0
+  int* ll = ctx->last_launch;
+  for (int k = 0; k < DIAL_LAUNCH_FIELDS; k++) ll[k] = 0;
+  ll[LF_INST] = ctx->inst;
+  ll[LF_ROLLOUTS] = B;
   if (int rc = check_sticky(ctx)) return rc;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (ctx->timing) {
@@ -957,6 +970,7 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
       // trajectory was measured here as well (N = 2048 as exactly 1024 wavefronts, one per SIMD): 0.418 ms against 0.389 ms with
       // the 1025th wavefront -- the hand-over code slows every wavefront more than the odd one costs (profiles/r05_ab_pair_n2048.txt)
       const int pairs = (B + 1) / 2;
+      ll[LF_PAIR] = 1; ll[LF_WPB] = 1; ll[LF_BLOCKS] = pairs;
       hipLaunchKernelGGL((rollout_kernel2<DimsGo2, 1, DIAL_GO2_PAIR_OCC, false, false>), dim3(pairs), dim3(64), ctx->lds_pair, st,
                          (const CModel<DimsGo2>*)ctx->dcm, (const dial_task*)ctx->dtask, (const dial_cfg*)ctx->dcfg, io, B, ctx->ws_words, (int*)nullptr);
     } else {
@@ -971,6 +985,7 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
         io.err_word = ctx->err_dev;
       }
       HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->next, blocks * DIAL_GO2_PAIR_WPB, 1, st));
+      ll[LF_PAIR] = 1; ll[LF_WPB] = DIAL_GO2_PAIR_WPB; ll[LF_BLOCKS] = blocks; ll[LF_QUEUE] = 1; ll[LF_MEAN_INLINE] = io.mean_inline;
       hipLaunchKernelGGL((rollout_kernel2<DimsGo2, DIAL_GO2_PAIR_WPB, DIAL_GO2_PAIR_OCC, true, true>), dim3(blocks), dim3(64 * DIAL_GO2_PAIR_WPB),
                          ctx->lds_pair_large, st, (const CModel<DimsGo2>*)ctx->dcm, (const dial_task*)ctx->dtask, (const dial_cfg*)ctx->dcfg, io, B,
                          ctx->ws_words, ctx->next);
@@ -992,6 +1007,7 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
   // (only when the noisy rollouts fill the SIMDs evenly and the mean trajectory is the odd one out: N = k x 1024; never in grouped
   //  launches, whose mean trajectories are rollouts N, 2 N + 1, ...: they -- and the interleaved mean trajectory, the split launch -- take
   //  the paths that treat every rollout alike)
+  bool relay = false;
   if (ctx->relay_ok && !large && !io.us && !io.plan_rollouts && io.n_noise == B - 1 && B > 1 && ctx->T >= 4 && ctx->n_simd > 0 &&
       ((B - 1) % ctx->n_simd == 0 || ctx->relay_always)) {
     const int pieces = (ctx->T + ctx->relay_steps - 1) / ctx->relay_steps;
@@ -1002,6 +1018,7 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
       io.relay_base = B - 1;
       io.err_word = ctx->err_dev;
       io.debug_stall_piece1 = ctx->debug_stall_piece1;
+      relay = true;
     }
   }
   int blocks = io.relay_flag ? io.relay_base + (ctx->T + io.relay_steps - 1) / io.relay_steps : (B + wpb - 1) / wpb;
@@ -1047,6 +1064,8 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
     if (B > ctx->trace_rows) return fail(ctx, DIAL_ERR_ARG, "rollout launch: more rollouts than rows of the state trace (dial_set_state_trace)");
     io.trace = ctx->trace;
   }
+  ll[LF_WPB] = wpb; ll[LF_BLOCKS] = blocks; ll[LF_QUEUE] = next != nullptr; ll[LF_RELAY] = relay; ll[LF_MEAN_INLINE] = io.mean_inline;
+  ll[LF_SLICE_PIECES] = io.slice_pieces; ll[LF_TRACE] = tracing; ll[LF_CON_CAP] = io.con_cap;
   // Batch = 8 x CUs + 1 (N = 2048 on 256 CUs) with multi-wavefront workgroups: the N noisy rollouts as evenly sized
   // workgroups that load every CU with 8 wavefronts (Allegro: one workgroup of 8, H1: two of 4, one wavefront per SIMD
   // each), the mean trajectory as a one-wavefront workgroup launched on the side stream (fork / join by events)
@@ -1055,6 +1074,7 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
     dial::RolloutIO io1 = io;
     io1.n_first = B - 1;
+    ll[LF_SPLIT] = 1; ll[LF_WPB] = ctx->wpb_even; ll[LF_BLOCKS] = (B - 1) / ctx->wpb_even;   // (+ the mean trajectory's one-wavefront workgroup)
 #define DIAL_SPLIT_LAUNCH(D, WPBE, OCCE)                                                                                       \
     hipLaunchKernelGGL((rollout_kernel<D, 1>), dim3(1), dim3(64), ctx->lds_one, ctx->side, (const CModel<D>*)ctx->dcm,     \
                        (const dial_task*)ctx->dtask, (const dial_cfg*)ctx->dcfg, io1, B, ctx->ws_words, (int*)nullptr);    \
@@ -1557,6 +1577,15 @@ int dial_debug_scratch(dial_ctx* ctx, float** Y0s, float** rewss, float** qss, f
   return DIAL_OK;
 }
 int dial_lds_bytes(dial_ctx* ctx) { return ctx ? (int)ctx->lds_rollout : -1; }
+// the shape of the context's most recent rollout launch, enum LaunchField order: instantiation (dial_ctx::inst), wavefronts per
+// workgroup, grid workgroups (0: the call returned before launching), rollout queue, mean-trajectory relay, interleaved mean trajectory,
+// time-slice pieces, split launch, pair kernel, state-trace instantiation, overflow cap in effect (0: no overflow areas), rollouts.
+// Copies min(n, fields) ints to out; returns the number of fields.
+int dial_debug_last_launch(dial_ctx* ctx, int* out, int n) {
+  if (!ctx || (n > 0 && !out)) return DIAL_ERR_ARG;
+  for (int k = 0; k < n && k < DIAL_LAUNCH_FIELDS; k++) out[k] = ctx->last_launch[k];
+  return DIAL_LAUNCH_FIELDS;
+}
 // tests: switch the relay-stall hook of DIAL_DEBUG_RELAY_STALL on (k >= 1: piece k - 1 never hands over) or off (0)
 int dial_debug_set_stall(dial_ctx* ctx, int piece1) { if (!ctx) return DIAL_ERR_ARG; ctx->debug_stall_piece1 = piece1; return DIAL_OK; }
 // wavefront slots of the rollout kernel on the whole chip for a batch of B rollouts (B > slots: the rollout queue runs)

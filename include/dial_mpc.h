@@ -334,7 +334,9 @@ typedef struct dial_options {
   int32_t force_generic;      /* 1: capacity-dimension (generic) kernel instantiation instead of the robot's own -- what a user model
                                  that is none of the seven runs on.  Its price, measured once with the Go2 (round 6, N = 2048 H = 16): 1.076
                                  ms per iteration against 0.347 ms on the robot's own kernel, i.e. 3.1 x (run-time dimensions, packed
-                                 triangles, the LDS phase version of the position stage; profiles/r06_bench_go2_on_capacity_dimension_kernel.json) */
+                                 triangles, the LDS phase version of the position stage; profiles/r06_bench_go2_on_capacity_dimension_kernel.json).
+                                 Pyramidal friction cones only: an elliptic-cone model (the Allegro hand) with force_generic = 1 is refused
+                                 (DIAL_ERR_UNSUPPORTED) -- the capacity-dimension kernel has no elliptic-cone solver                   */
   int32_t con_cap;            /* generic instantiation, models with many candidate contacts: touching contacts the LDS
                                  workspace of a rollout wavefront holds (samples beyond run on an overflow area in global
                                  memory, bit-identically).  0: chosen per model (largest of 16 .. 8 that keeps nine wavefronts

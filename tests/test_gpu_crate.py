@@ -223,27 +223,38 @@ def test_crate_overflow_path_under_the_relay_at_full_size():
     """at the example's N = 2048 the mean trajectory runs as relay pieces, i.e. the grid holds MORE wavefronts
     (N + pieces) than rollouts (N + 1), and every wavefront slot owns an overflow area.  con_cap = 1 makes every touching step
     of every wavefront -- the relay pieces included -- use its area: results must equal the default cap's bit for bit, and
-    a batch beyond the context's capacity must be refused instead of overrunning the areas."""
+    a batch beyond the context's capacity must be refused instead of overrunning the areas.
+    The relay needs one wavefront per workgroup: the scene's own instantiation (DimsGo2Crate, nine wavefronts per workgroup) never
+    relays, so its leg states that it ran the plain grid; the relay claim is the capacity-dimension leg's (force_generic), where
+    debug_last_launch shows the relay pieces."""
     import torch
     from dial_mpc_amd import _lib
     N, H = 2048, 25
+    pieces = (H + 1 + 2) // 3
     dc, env, model, task, cfg = setup_case(EX, N, H)
-    outs = {}
-    for cap in (0, 1):
-        ctx = _lib.Context(model, task, cfg, options=dict(con_cap=cap))
-        assert ctx.lib.dial_debug_resident_rollouts(ctx.h, N + 1) >= N + 1 + (H + 3) // 3      # everything resident: the relay runs
-        s0, _, _ = ctx.env_reset(_dev(env._init_q), _dev(np.zeros(model.nv)))
-        eps, sigma, Ybar = seeded_inputs(dc, model.nu, seed=5, Ybar_scale=0.2)
-        out = ctx.reverse_once(s0, _dev(Ybar), _dev(sigma), _dev(eps))
-        torch.cuda.synchronize()
-        ctx.status()
-        sc = ctx.debug_scratch()
-        outs[cap] = (out["Ybar"].cpu().numpy(), out["rews"].cpu().numpy(), sc["qss"].copy(), sc["rewss"].copy())
-        if cap == 1:
-            us = torch.zeros((N + H + 8, H + 1, model.nu), device="cuda")
-            with pytest.raises(_lib.DialHipError, match="overflow areas"):
-                ctx.rollout(s0, us)
-        del ctx
-    assert np.all(np.isfinite(outs[0][1]))
-    for a, b in zip(outs[0], outs[1]):
-        assert np.array_equal(a, b)
+    for generic in (0, 1):
+        outs = {}
+        for cap in (0, 1):
+            ctx = _lib.Context(model, task, cfg, options=dict(con_cap=cap, force_generic=generic))
+            assert ctx.lib.dial_debug_resident_rollouts(ctx.h, N + 1) >= N + 1 + (H + 3) // 3      # everything resident: no queue
+            s0, _, _ = ctx.env_reset(_dev(env._init_q), _dev(np.zeros(model.nv)))
+            eps, sigma, Ybar = seeded_inputs(dc, model.nu, seed=5, Ybar_scale=0.2)
+            out = ctx.reverse_once(s0, _dev(Ybar), _dev(sigma), _dev(eps))
+            torch.cuda.synchronize()
+            ctx.status()
+            ll = ctx.debug_last_launch()
+            if generic:   # capacity-dimension kernel: the relay runs, N noisy wavefronts + the mean trajectory's pieces
+                assert (ll["inst"], ll["wpb"], ll["relay"], ll["queue"], ll["blocks"]) == (0, 1, 1, 0, N + pieces), ll
+            else:         # the scene's own kernel: nine wavefronts per workgroup, no relay
+                assert (ll["inst"], ll["wpb"], ll["relay"], ll["queue"], ll["blocks"]) == (5, 9, 0, 0, (N + 1 + 8) // 9), ll
+            assert (ll["con_cap"] == 1) if cap == 1 else (ll["con_cap"] > 0), ll   # (52 candidate contacts: overflow areas either way)
+            sc = ctx.debug_scratch()
+            outs[cap] = (out["Ybar"].cpu().numpy(), out["rews"].cpu().numpy(), sc["qss"].copy(), sc["rewss"].copy(), sc["qdss"].copy())
+            if cap == 1 and not generic:
+                us = torch.zeros((N + H + 8, H + 1, model.nu), device="cuda")
+                with pytest.raises(_lib.DialHipError, match="overflow areas"):
+                    ctx.rollout(s0, us)
+            del ctx
+        assert np.all(np.isfinite(outs[0][1]))
+        for a, b in zip(outs[0], outs[1]):
+            assert np.array_equal(a, b), f"force_generic={generic}"

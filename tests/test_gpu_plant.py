@@ -23,6 +23,9 @@ def _dev(x, dtype=np.float32):
     return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype), device="cuda:0")
 
 
+GEN = dict(force_generic=1)   # dial_options: the capacity-dimension instantiation (DimsMax, kernel instantiation 0) and its plant kernel
+
+
 def _case(example, pd):
     """(model, task) of the example at sim_dt with one physics step per step, and the oracle's action mapping made the identity up to
     the factor R: joint_offset 0, joint_range = phys_range = [-R, R], action_scale 1 -> act2joint(c / R) = c for dyadic c."""
@@ -73,20 +76,32 @@ def _clocks(M):
     return t, plan_time
 
 
-@pytest.mark.parametrize("example,pd", [("unitree_go2_trot", False), ("unitree_h1_jog", False), ("unitree_h1_loco", False),
-                                        ("allegro_reorient", False), ("unitree_go2_crate_climb", False),
-                                        ("unitree_go2_trot", True), ("unitree_h1_jog", True), ("unitree_h1_loco", True),
-                                        ("unitree_go2_crate_climb", True)])
-def test_plant_matches_the_oracle(example, pd):
+# the kernel instantiation each case's plant runs on (dial_hip.hip: dial_ctx::inst)
+INST = {"unitree_go2_trot": 1, "unitree_h1_jog": 2, "unitree_h1_loco": 3, "allegro_reorient": 4, "unitree_go2_crate_climb": 5,
+        "unitree_h1_push_crate": 6}
+PLANT_CASES = [pytest.param(ex, pd, None, id=f"{ex}-{pd}")
+               for ex, pd in [("unitree_go2_trot", False), ("unitree_h1_jog", False), ("unitree_h1_loco", False), ("allegro_reorient", False),
+                              ("unitree_go2_crate_climb", False), ("unitree_go2_trot", True), ("unitree_h1_jog", True),
+                              ("unitree_h1_loco", True), ("unitree_go2_crate_climb", True), ("unitree_h1_push_crate", False),
+                              ("unitree_h1_push_crate", True)]]
+PLANT_CASES += [pytest.param(ex, pd, GEN, id=f"{ex}-{pd}-generic")
+                for ex, pd in [("unitree_go2_trot", False), ("unitree_go2_trot", True), ("unitree_h1_loco", False)]]
+
+
+@pytest.mark.parametrize("example,pd,options", PLANT_CASES)
+def test_plant_matches_the_oracle(example, pd, options):
     """K = 4 steps at sim_dt = 0.005 of 64 plants against Oracle.rollout (fp32) over the same steps, each step's row chosen by
     ctrl_row on the host clock.  Gate per plant and step: within the per-rollout tolerance, or the whole plant reproduced by the oracle
-    under <= 64 ulp of state jitter (rollout_jitter); the witnessed share is capped like the rollout tests'."""
+    under <= 64 ulp of state jitter (rollout_jitter); the witnessed share is capped like the rollout tests'.
+    options=GEN: the same on the capacity-dimension plant kernel (plant_kernel<DimsMax>), and then its final state after one K = 16
+    launch without a trace against the oracle's state after the same 16 steps, under the same rule."""
     import oracle as O
     from dial_mpc_amd import _lib
     from dial_mpc_amd.deploy.plant import ctrl_row
     env, model, task = _case(example, pd)
     M, K = 64, 4
-    ctx = _lib.Context(model, task, None, device=0)
+    ctx = _lib.Context(model, task, None, device=0, options=options)
+    assert ctx.debug_last_launch()["inst"] == (0 if options else INST[example])
     o32 = O.Oracle(model, task, None, np.float32)
     states = _start_states(ctx, env, M, seed=1)
     s0 = states.cpu().numpy().copy()
@@ -115,20 +130,53 @@ def test_plant_matches_the_oracle(example, pd):
         witnessed.append(m)
     assert len(witnessed) <= max(1, int(KNIFE_EDGE_FRAC[example] * M)), witnessed
     assert np.isfinite(got_s).all()
+    if options:
+        K2 = 16
+        states = _start_states(ctx, env, M, seed=1)
+        tt = _dev(t, np.float64)
+        ctx.plant_step(states, tt, _dev(plan_time), _dev(rows), CTRL_DT, SIM_DT, K2, _lib.PLANT_PD if pd else _lib.PLANT_CTRL)
+        got_s, t_end = states.cpu().numpy(), tt.cpu().numpy()
+        verdicts = []
+        for m in range(M):
+            tm, ks = t[m], []
+            for _ in range(K2):
+                ks.append(ctrl_row(tm, plan_time[m], CTRL_DT, T))
+                tm += SIM_DT
+            assert t_end[m] == tm, m
+            us = (rows[m, ks] / np.float32(R))[None]
+            v = _final_follows_oracle(o32, s0[m], us, got_s[m, :nq], got_s[m, nq:nq + nv])
+            assert v != "unwitnessed", f"{example} generic: plant {m}'s state after {K2} steps leaves the oracle and no jittered run follows it"
+            verdicts.append(v)
+        assert sum(v == "witnessed" for v in verdicts) <= max(1, int(KNIFE_EDGE_FRAC[example] * M)), verdicts
 
 
-def _plant_ctx(example):
+def _final_follows_oracle(o32, s0, us, q, qd):
+    """A plant's final q / qd against the oracle's state after the same steps (Oracle.rollout): within the per-rollout tolerance
+    (None), or reproduced by one of 16 oracle runs under <= 64 ulp of state jitter ("witnessed"), or neither ("unwitnessed")."""
+    def follows(roll):
+        return _within(q, roll[1][0][-1], TOL["q"]).all() and _within(qd, roll[2][0][-1], TOL["qd"]).all()
+    if follows(o32.rollout(s0, us)):
+        return None
+    if any(follows(o32.rollout_jitter(s0, us, noise_seed=7919 * (j + 1), noise_mag=64.0)) for j in range(16)):
+        return "witnessed"
+    return "unwitnessed"
+
+
+def _plant_ctx(example, options=None):
     from dial_mpc_amd import _lib
     env, model, task = _case(example, False)
-    return env, _lib.Context(model, task, None, device=0)
+    return env, _lib.Context(model, task, None, device=0, options=options)
 
 
-@pytest.mark.parametrize("example", ["unitree_go2_trot", "unitree_h1_loco", "unitree_go2_crate_climb", "allegro_reorient"])
-def test_plant_bit_identities(example):
+@pytest.mark.parametrize("example,options", [pytest.param(ex, None, id=ex) for ex in ["unitree_go2_trot", "unitree_h1_loco", "unitree_go2_crate_climb",
+                                                                                     "allegro_reorient", "unitree_h1_push_crate"]]
+                         + [pytest.param("unitree_go2_trot", GEN, id="unitree_go2_trot-generic")])
+def test_plant_bit_identities(example, options):
     """M plants in one launch = each plant alone; one K = 4 launch = four K = 1 launches (warm start included)."""
     import torch
     from dial_mpc_amd import _lib
-    env, ctx = _plant_ctx(example)
+    env, ctx = _plant_ctx(example, options)
+    assert ctx.debug_last_launch()["inst"] == (0 if options else INST[example])
     M = 8
     s0 = _start_states(ctx, env, M, seed=3)
     rows, (t, plan_time) = _dev(_rows(env, M, False, seed=4)), _clocks(M)
