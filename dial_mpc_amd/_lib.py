@@ -201,6 +201,11 @@ def load(path: Optional[str] = None):
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack per-plan task parameters)
             raise
     try:
+        lib.dial_user_control.argtypes = [vp, fp, fp, ci, fp, vp]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack user control laws)
+            raise
+    try:
         lib.dial_plant_step.argtypes = [vp, fp, fp, fp, fp, ci, ctypes.c_double, ctypes.c_double, ci, ci, fp, ci, vp]
     except AttributeError:
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack the plant simulator)
@@ -231,7 +236,7 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
             "dial_shard_ybar_gathered", "dial_shard_ybar_gathered_rng", "dial_shard_reduce_gathered", "dial_shift", "dial_env_step", "dial_env_reset", "dial_env_reset_batch",
             "dial_status", "dial_set_timing", "dial_get_rollout_ms", "dial_abi_sizes",
             "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch",
-            "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params", "dial_plant_step")
+            "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params", "dial_plant_step", "dial_user_control")
 
 # dial_plant_step flags (include/dial_mpc.h)
 PLANT_CTRL, PLANT_PD, PLANT_HOLD_FIRST = (_abi.MACROS[k] for k in ("DIAL_PLANT_CTRL", "DIAL_PLANT_PD", "DIAL_PLANT_HOLD_FIRST"))
@@ -347,6 +352,17 @@ class Context:
         self._check(self.lib.dial_set_plan_params(self.h, dev.data_ptr(), int(dev.shape[0])), "dial_set_plan_params")
         self._plan_params = dev
         return dev
+
+    def user_control(self, states, actions):
+        """The user control law of a task-plugin context (dial_user_control) for n rows in one launch: states [n, state_size] packed,
+        actions [n, nu] -> ctrl [n, nu], what env_step would hand the actuators from row g's state with row g's action.  With per-plan
+        parameters bound, row g reads parameter row g.  Raises DialHipError on a context without a law."""
+        import torch
+        n = int(states.shape[0])
+        assert tuple(states.shape) == (n, self.state_size) and tuple(actions.shape) == (n, self.nu)
+        ctrl = torch.empty((n, self.nu), dtype=torch.float32, device=self.torch_device)
+        self._check(self.lib.dial_user_control(self.h, _ptr(states), _ptr(actions), n, _ptr(ctrl), _stream()), "dial_user_control")
+        return ctrl
 
     def __del__(self):
         try:

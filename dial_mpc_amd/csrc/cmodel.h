@@ -156,6 +156,8 @@ struct Dims {
 #endif
   // a user reward (DIAL_TASK_USER, csrc/user_reward.h) instead of the built-in ones: the instantiations of a task plugin only (DimsUser)
   static constexpr bool user = false;
+  // a user control law (csrc/user_control.h) in place of act2joint / the PD law: a task plugin built with one (DimsUser's last parameter)
+  static constexpr bool user_ctrl = false;
 };
 using DimsGo2 = Dims<true, 19, 18, 12, 14, 13, 5, 5, 4, 12, TopoGo2, true, 192>;
 using DimsH1 = Dims<true, 26, 25, 19, 21, 20, 3, 3, 4, 19, TopoH1, true, 256>;
@@ -168,10 +170,12 @@ using DimsH1PushCrate = Dims<true, 27, 26, 19, 22, 21, 9, 3, 28, 19, TopoH1PushC
 using DimsMax = Dims<false, DIAL_MAX_Q, DIAL_MAX_V, DIAL_MAX_U, DIAL_MAX_BODY, DIAL_MAX_JNT, DIAL_MAX_GEOM,
                      DIAL_MAX_SITE, DIAL_MAX_CON, DIAL_MAX_LIM>;
 // A task plugin's instantiation (dial_mpc_amd/plugin.py): the generic feature set at the model's compile-time dimensions, dense
-// dof order, constants staged in LDS, and the user reward in place of the built-in ones (rollout_body.h: env_step)
-template <int NQ_, int NV_, int NU_, int NB_, int NJ_, int NG_, int NS_, int NC_, int NL_, int NFRI_>
+// dof order, constants staged in LDS, and the user reward in place of the built-in ones (rollout_body.h: env_step); USER_CTRL_:
+// the plugin also carries a user control law
+template <int NQ_, int NV_, int NU_, int NB_, int NJ_, int NG_, int NS_, int NC_, int NL_, int NFRI_, bool USER_CTRL_ = false>
 struct DimsUser : Dims<true, NQ_, NV_, NU_, NB_, NJ_, NG_, NS_, NC_, NL_, TopoDense, false, 2, false, 0, 4, true, NFRI_, true> {
   static constexpr bool user = true;
+  static constexpr bool user_ctrl = USER_CTRL_;
 };
 
 // compile-time loop: f(std::integral_constant<int, I>) for I in [B, E)
@@ -211,10 +215,17 @@ struct CModelGeneric<D, true> {
 };
 
 // What only a task plugin's instantiation carries: the user reward's parameters (dial_set_user_params).  An EMPTY base elsewhere.
+// With a user control law: the dof each actuator drives (the inverse of dof_act; the law reads its own joint's velocity through it).
+template <class D, bool USER_CTRL = D::user_ctrl>
+struct CModelUserCtrl {};
+template <class D>
+struct CModelUserCtrl<D, true> {
+  int32_t act_dofadr[D::NU];
+};
 template <class D, bool USER = D::user>
 struct CModelUser {};
 template <class D>
-struct CModelUser<D, true> {
+struct CModelUser<D, true> : CModelUserCtrl<D> {
   float user_params[DIAL_USER_PARAMS];
 };
 

@@ -348,6 +348,7 @@ struct dial_ctx {
   int inst = 0;               // 0 generic (DimsMax), 1 Go2, 2 H1, 3 H1 loco, 4 Allegro (elliptic cones), 5 Go2 crate climb, 6 H1 push crate,
                               // 7 a task plugin's instantiation (dial_create_plugin: `plug`)
   const dial_plugin_ops* plug = nullptr;   // inst 7: the plugin's host functions (the library stays loaded for the process)
+  const dial_plugin_ctrl* plug_ctrl = nullptr;   // inst 7: the plugin's user control law (dial_user_control), nullptr when it has none
   std::vector<char> plug_cm;               // inst 7: host copy of the constants (dial_set_user_params rewrites the parameters)
   const float* plan_params = nullptr;      // inst 7: per-plan task parameters (dial_set_plan_params), caller-owned device rows ...
   int plan_rows = 0;                       // ... [plan_rows, DIAL_USER_PARAMS]; nullptr: every launch reads the shared ones
@@ -490,7 +491,35 @@ int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task*
   const int md[10] = {model->nq, model->nv, model->nu, model->nbody, model->njnt, model->ngeom, model->nsite, model->ncon, model->nlim, model->nfri};
   for (int k = 0; k < 10; k++)
     if (md[k] != ops->dims[k]) return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the model's dimensions differ from the plugin's (rebuild the plugin for this model)");
-  return create_impl(out, model, task, cfg, device, -1, opts, ops, params, n_params);
+  // the user control law's table: a second symbol, absent from a plugin built without a law
+  const dial_plugin_ctrl* ctl = nullptr;
+  if (dial_plugin_ctrl_entry centry = (dial_plugin_ctrl_entry)dlsym(h, DIAL_PLUGIN_CTRL_SYMBOL)) {
+    ctl = centry();
+    if (!ctl) return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + plugin_path + ": " DIAL_PLUGIN_CTRL_SYMBOL " returned no table");
+    if (ctl->version != DIAL_PLUGIN_CTRL_VERSION)
+      return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: stale plugin: its control-law table reports version ") + std::to_string(ctl->version) +
+                                         ", the library needs version " + std::to_string(DIAL_PLUGIN_CTRL_VERSION) + " (rebuild it from the current sources)");
+    if (ctl->cmodel_bytes != ops->cmodel_bytes || ctl->sizeof_control_in != sizeof(DialControlIn) || ctl->nq != model->nq || ctl->nv != model->nv ||
+        ctl->nu != model->nu)
+      return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's control-law table was built against another version of the library (ABI mismatch; rebuild it)");
+  }
+  const int rc = create_impl(out, model, task, cfg, device, -1, opts, ops, params, n_params);
+  if (rc == DIAL_OK) (*out)->plug_ctrl = ctl;
+  return rc;
+}
+
+int dial_user_control(dial_ctx* ctx, const float* states, const float* actions, int n, float* ctrl_out, void* stream) {
+  if (!ctx || !states || !actions || !ctrl_out) return fail(ctx, DIAL_ERR_ARG, "dial_user_control: null argument");
+  if (!ctx->plug_ctrl)
+    return fail(ctx, DIAL_ERR_ARG, ctx->plug ? "dial_user_control: the context's task plugin was built without a user control law (build_plugin(control_src=))"
+                                             : "dial_user_control: the context has no task plugin (dial_create_plugin), so no user control law");
+  if (n < 1) return fail(ctx, DIAL_ERR_ARG, "dial_user_control: n = " + std::to_string(n) + " rows; n must be at least 1");
+  if (ctx->plan_params && n > ctx->plan_rows)
+    return fail(ctx, DIAL_ERR_ARG, "dial_user_control: n = " + std::to_string(n) + " exceeds the " + std::to_string(ctx->plan_rows) +
+                                   " rows of per-plan task parameters bound with dial_set_plan_params");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->plug_ctrl->user_control(n, (hipStream_t)stream, ctx->dcm, states, actions, ctrl_out, ctx->plan_params));
+  return DIAL_OK;
 }
 
 int dial_set_user_params(dial_ctx* ctx, const float* params, int n) {

@@ -3,14 +3,23 @@
 // them (plugin_ops.h, dial_create_plugin).  The build generates two files next to its objects:
 //   dial_plugin_dims.h    #define DIAL_PLUGIN_NQ ... DIAL_PLUGIN_NFRI  (the model's dimensions)
 //   dial_user_reward.hip  the user's definition of dial_user_reward (user_reward.h states the contract)
+// and, for a plugin with a user control law (-DDIAL_PLUGIN_USER_CTRL=1), a third:
+//   dial_user_control.hip the user's definition of dial_user_control (user_control.h states the contract)
+// Such a plugin carries one more kernel, user_control_kernel, and exports a second table (plugin_ops.h: dial_plugin_ctrl).
 #include "plugin_ops.h"
 #include "dial_plugin_dims.h"
 #include "dial_user_reward.hip"
+#ifndef DIAL_PLUGIN_USER_CTRL
+#define DIAL_PLUGIN_USER_CTRL 0
+#endif
+#if DIAL_PLUGIN_USER_CTRL
+#include "dial_user_control.hip"
+#endif
 
 // one wavefront per workgroup (the capacity-dimension kernel's shape): the mean-trajectory relay applies, no split launches
 #define DIAL_PLUGIN_WPB 1
 using DimsPlugin = DimsUser<DIAL_PLUGIN_NQ, DIAL_PLUGIN_NV, DIAL_PLUGIN_NU, DIAL_PLUGIN_NB, DIAL_PLUGIN_NJ, DIAL_PLUGIN_NG, DIAL_PLUGIN_NS,
-                            DIAL_PLUGIN_NC, DIAL_PLUGIN_NL, DIAL_PLUGIN_NFRI>;
+                            DIAL_PLUGIN_NC, DIAL_PLUGIN_NL, DIAL_PLUGIN_NFRI, DIAL_PLUGIN_USER_CTRL != 0>;
 
 template __global__ void rollout_kernel<DimsPlugin, DIAL_PLUGIN_WPB, 3, false, false>(const CModel<DimsPlugin>*, const dial_task*, const dial_cfg*,
                                                                                   dial::RolloutIO, int, int, int*);
@@ -25,3 +34,11 @@ template __global__ void env_reset_kernel<DimsPlugin>(const CModel<DimsPlugin>*,
 extern "C" __attribute__((visibility("default"))) const dial_plugin_ops* dial_plugin_ops_v1(void) {
   return PluginOps<DimsPlugin, DIAL_PLUGIN_WPB>::table();
 }
+
+#if DIAL_PLUGIN_USER_CTRL
+template __global__ void user_control_kernel<DimsPlugin>(const CModel<DimsPlugin>*, const float*, const float*, float*, const float*);
+
+extern "C" __attribute__((visibility("default"))) const dial_plugin_ctrl* dial_plugin_ctrl_v1(void) {
+  return PluginCtrl<DimsPlugin>::table();
+}
+#endif

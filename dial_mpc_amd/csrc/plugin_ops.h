@@ -52,6 +52,52 @@ struct dial_plugin_ops {
 
 typedef const dial_plugin_ops* (*dial_plugin_entry)(void);
 
+// A plugin built with a user control law (user_control.h) exports a SECOND table under a second symbol; dial_plugin_ops and its ABI
+// version stay as they are, and a plugin without a law does not export the symbol (dial_create_plugin: the context has no law).
+#define DIAL_PLUGIN_CTRL_VERSION 1
+#define DIAL_PLUGIN_CTRL_SYMBOL "dial_plugin_ctrl_v1"
+struct dial_plugin_ctrl {
+  int version;                     // DIAL_PLUGIN_CTRL_VERSION
+  int nq, nv, nu;                  // of the instantiation (the row strides of the launch below)
+  size_t cmodel_bytes;             // sizeof(CModel<D>): the same constants as dial_plugin_ops' (ABI check)
+  size_t sizeof_control_in;        // sizeof(DialControlIn)
+  // the law for n rows: states [n, nq + 2 nv + DIAL_INFO_N] packed, actions [n, nu] -> ctrl_out [n, nu]; row g reads row g of
+  // plan_params ([n, DIAL_USER_PARAMS]) or, nullptr, the shared parameters of the constants
+  hipError_t (*user_control)(int n, hipStream_t st, const void* dcm, const float* states, const float* actions, float* ctrl_out,
+                             const float* plan_params);
+};
+typedef const dial_plugin_ctrl* (*dial_plugin_ctrl_entry)(void);
+
+// The user control law outside a step: one 64-lane workgroup per row of (packed state, action), lane a evaluates actuator a exactly as
+// env_step's control phase does -- same inputs (the row's qpos / qvel / step counter / info_user slots), constants read from global
+// memory (nothing is staged: a row is one call of the law per lane).
+template <class D>
+__global__ void __launch_bounds__(64)
+user_control_kernel(const CModel<D>* __restrict__ gm, const float* __restrict__ states, const float* __restrict__ actions,
+                    float* __restrict__ ctrl_out, const float* __restrict__ plan_params) {
+  static_assert(D::user_ctrl && D::NU <= 64, "a task plugin's instantiation with a control law; one lane per actuator");
+  const int g = (int)blockIdx.x, a = (int)threadIdx.x;
+  if (a >= D::NU) return;
+  const float* const st = states + (size_t)g * (D::NQ + 2 * D::NV + DIAL_INFO_N);
+  const float* const info = st + D::NQ + 2 * D::NV;
+  const float* const params = plan_params ? plan_params + (size_t)g * DIAL_USER_PARAMS : gm->user_params;
+  const DialControlIn in = dial::control_in(gm, info[DIAL_INFO_STEP], st, st + D::NQ, actions + (size_t)g * D::NU);
+  ctrl_out[(size_t)g * D::NU + a] = dial_user_control(in, a, params, info + DIAL_INFO_USER);
+}
+
+template <class D>
+struct PluginCtrl {
+  static hipError_t user_control(int n, hipStream_t st, const void* dcm, const float* states, const float* actions, float* ctrl_out,
+                                 const float* plan_params) {
+    hipLaunchKernelGGL(user_control_kernel<D>, dim3(n), dim3(64), 0, st, (const CModel<D>*)dcm, states, actions, ctrl_out, plan_params);
+    return hipGetLastError();
+  }
+  static const dial_plugin_ctrl* table() {
+    static const dial_plugin_ctrl ctl = {DIAL_PLUGIN_CTRL_VERSION, D::NQ, D::NV, D::NU, sizeof(CModel<D>), sizeof(DialControlIn), &user_control};
+    return &ctl;
+  }
+};
+
 // ---- the table of one instantiation D (rollout kernels with WPB wavefronts per workgroup, occupancy target 3)
 template <class D, int WPB>
 struct PluginOps {
@@ -100,6 +146,7 @@ struct PluginOps {
   static void fill(void* host_cm, const dial_model* m, const dial_task* t, const dial_derived* dv, const float* params, int n) {
     CModel<D>* c = new (host_cm) CModel<D>();
     fill_cmodel(c, m, t, dv);
+    if constexpr (D::user_ctrl) { for (int a = 0; a < D::NU; a++) c->act_dofadr[a] = m->act_dofadr[a]; }
     set_params(c, params, n);
   }
   static hipError_t set_lds(size_t lds) {

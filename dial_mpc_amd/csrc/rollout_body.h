@@ -217,6 +217,7 @@ DIAL_DEV void make_frame(float* fr, const float* a_in) {
 #include "solver_reg2.h"
 #include "smooth_quad2.h"
 #include "user_reward.h"
+#include "user_control.h"
 namespace dial {
 
 // Generic instantiation: x = A^-1 rhs for the packed SPD matrix A (M or H) with the register-resident L D L^T of
@@ -1778,6 +1779,12 @@ DIAL_DEV float act2joint(const M* m, float act, int a) {
   float jt = (m->joint_range[a][0] + m->joint_offset[a]) + an * (m->joint_range[a][1] - m->joint_range[a][0]);
   return dm::clip(jt, m->phys_range[a][0], m->phys_range[a][1]);
 }
+// what a user control law reads (user_control.h), from the constants `m` and the state / action arrays of the caller
+template <class M>
+DIAL_DEV DialControlIn control_in(const M* m, float step, const float* qpos, const float* qvel, const float* act) {
+  return DialControlIn{dim_nq(m), dim_nv(m), dim_nu(m), step, m->dt, qpos, qvel, act, m->act_qposadr, m->act_dofadr, m->action_scale,
+                       m->kp, m->kd, &m->joint_range[0][0], &m->phys_range[0][0], &m->tau_range[0][0], m->joint_offset};
+}
 // get_foot_step for foot f at the (pre-increment) step counter `step` (function_utils.py:18-43)
 template <class M>
 DIAL_DEV float gait_ztar(const M* m, int f, float step) {
@@ -1795,6 +1802,15 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
   // act2joint / act2tau (base_env.py:38-66) | desired foot heights from the gait clock (get_foot_step)
   if constexpr (PRE) {
     w.jrow = s.jtab + st * nu;   // act2tau runs in the position stage's actuation lanes (smooth_quad.h: MO)
+  } else if constexpr (M::D::user_ctrl) {
+    // a task plugin's user control law (user_control.h) in place of act2joint / the PD law: lane a evaluates actuator a from the state
+    // the step starts from; position_control, kp and kd decide nothing here (a plugin has no gait clock: nothing else in this phase)
+    w.items(nu, [&](int a) {
+      const DialControlIn in = control_in(m, s.info[DIAL_INFO_STEP], s.qpos, s.qvel, s.act);
+      const float c = dial_user_control(in, a, m->user_params, s.info + DIAL_INFO_USER);
+      s.ctrl[a] = c;
+      s.info[DIAL_INFO_LAST_CTRL + a] = c;
+    });
   } else
   w.items(nu + DIAL_MAX_FEET, [&](int it) {
     if (it < nu) {

@@ -8,11 +8,17 @@ A subclass sets
   ``reward_hip``   the reward's HIP source, or the path of a ``.hip`` file (relative as above),
   ``user_params``  names of float fields of its config dataclass; their values, in this order, are the reward's ``params``,
   ``init_keyframe`` the model keyframe env.reset starts from (default "home"),
-and registers itself with ``dial_mpc_amd.envs.register_environment`` / ``register_config``.  Control is BaseEnv's
-(act2joint / act2tau with the config's leg_control, kp, kd, action_scale); the sampling range is the joint range of the model
-unless the subclass sets ``self.joint_range``.  Under ``leg_control: torque`` the PD law reads actuator a's joint as qpos[7 + a] /
-qvel[6 + a] (BaseEnv.act2tau): the model must have a free base joint and actuators that drive dofs 6, 7, ... in order; a model
-that does not is refused (``torque_joint_convention``).
+  ``control_hip``  optional: a control law as HIP source or the path of a ``.hip`` file (the contract of csrc/user_control.h),
+and registers itself with ``dial_mpc_amd.envs.register_environment`` / ``register_config``.  Without ``control_hip`` control is
+BaseEnv's (act2joint / act2tau with the config's leg_control, kp, kd, action_scale); the sampling range is the joint range of the
+model unless the subclass sets ``self.joint_range``.  Under ``leg_control: torque`` the PD law reads actuator a's joint as
+qpos[7 + a] / qvel[6 + a] (BaseEnv.act2tau): the model must have a free base joint and actuators that drive dofs 6, 7, ... in
+order; a model that does not is refused (``torque_joint_convention``).
+
+With ``control_hip`` the law replaces that block in every kernel of the plugin: it returns what each actuator receives, from the
+state the control step starts from, the action, the actuators' joint addresses and the task's control constants.  leg_control,
+kp and kd then decide nothing by themselves (the law may read kp and kd), the joint convention above is not required, and the
+host never restates the law: ``control(state, acts)`` and ``act2tau`` evaluate it on the device.
 """
 from __future__ import annotations
 
@@ -48,6 +54,7 @@ class CustomEnv(BaseEnv):
     task_kind = TASK_USER
     model_path: str = ""
     reward_hip: str = ""
+    control_hip: str = ""
     user_params: Sequence[str] = ()
     init_keyframe: str = "home"
 
@@ -55,7 +62,7 @@ class CustomEnv(BaseEnv):
         if not self.model_path or not self.reward_hip:
             raise TypeError(f"{type(self).__name__}: a CustomEnv subclass sets model_path and reward_hip")
         super().__init__(config)
-        if config.leg_control == "torque":
+        if config.leg_control == "torque" and not self.control_hip:   # (a control law indexes its own joints)
             torque_joint_convention(self.sys.model)
         self._init_q = np.asarray(self.sys.model["keyframes"][self.init_keyframe], dtype=np.float64)
         self._plugin = None
@@ -71,11 +78,17 @@ class CustomEnv(BaseEnv):
         model = mjcf.compile_mjcf(path) if path.endswith(".xml") else mjcf.model_from_json(open(path).read())
         return System(model).tree_replace({"opt.timestep": config.timestep})
 
-    def reward_source(self) -> str:
-        src = self.reward_hip
+    def _source(self, src: str) -> str:
         if "\n" not in src and src.endswith(".hip"):
             return open(self._resolve(src)).read()
         return src
+
+    def reward_source(self) -> str:
+        return self._source(self.reward_hip)
+
+    def control_source(self):
+        """The control law's HIP source, or None when the env uses BaseEnv's control."""
+        return self._source(self.control_hip) if self.control_hip else None
 
     def user_param_vector(self) -> List[float]:
         return [float(getattr(self._config, name)) for name in self.user_params]
@@ -87,8 +100,35 @@ class CustomEnv(BaseEnv):
         """Build (or find in the cache) this env's task plugin."""
         if self._plugin is None:
             from dial_mpc_amd.plugin import build_plugin
-            self._plugin = build_plugin(self.sys.model, self.reward_source())
+            self._plugin = build_plugin(self.sys.model, self.reward_source(), control_src=self.control_source())
         return self._plugin
+
+    def control(self, state, acts):
+        """The control law for T actions from one state, in one launch: acts [T, nu] (or [nu]) -> device tensor [T, nu] of what the
+        actuators would receive if env.step ran from `state` with each action -- the law sees the state's qpos / qvel, step counter and
+        user info slots.  Needs control_hip."""
+        import torch
+        if not self.control_hip:
+            raise TypeError(f"{type(self).__name__} has no control law (control_hip); use act2joint / act2tau")
+        ctx = self._context()
+        packed = state.packed if hasattr(state, "packed") else state
+        packed = torch.as_tensor(packed, dtype=torch.float32, device=ctx.torch_device)
+        acts = torch.as_tensor(acts, dtype=torch.float32, device=ctx.torch_device).reshape(-1, self.sys.nu).contiguous()
+        return ctx.user_control(packed.reshape(1, -1).expand(acts.shape[0], -1).contiguous(), acts)
+
+    def act2tau(self, act, pipeline_state):
+        """With control_hip: the law on the device from pipeline_state's qpos / qvel, at step 0 and with ZERO user info slots (a
+        pipeline_state carries no env info) -> numpy [nu].  A law that reads the step counter or the slots: use control(state, acts)."""
+        if not self.control_hip:
+            return super().act2tau(act, pipeline_state)
+        import torch
+        from dial_mpc_amd.envs.base_env import _to_numpy
+        ctx = self._context()
+        nq, nv = self.sys.nq, self.sys.nv
+        packed = np.zeros(ctx.state_size, np.float32)
+        packed[:nq] = np.asarray(_to_numpy(pipeline_state.qpos), dtype=np.float32)
+        packed[nq:nq + nv] = np.asarray(_to_numpy(pipeline_state.qvel), dtype=np.float32)
+        return self.control(torch.as_tensor(packed, device=ctx.torch_device), np.asarray(_to_numpy(act), dtype=np.float32))[0].cpu().numpy()
 
     def context_kwargs(self) -> Dict[str, Any]:
         """What a _lib.Context of this env needs beyond (model, task, cfg): its plugin and parameters."""

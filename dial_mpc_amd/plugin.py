@@ -1,10 +1,12 @@
-"""Task plugins: a user reward compiled, for one model, into the rollout / env.step / env.reset kernels (HIP, gfx950).
+"""Task plugins: a user reward -- and optionally a user control law -- compiled, for one model, into the rollout / env.step /
+env.reset kernels (HIP, gfx950).
 
 ``build_plugin(model, reward_src)`` writes the model's dimensions and the reward source next to ``csrc/plugin.hip``'s object,
 compiles that one translation unit with the product flags (``_lib._COMMON + _FAST``) and links a shared library that
 ``libdialhip.so`` loads (``dial_create_plugin``; ``_lib.Context(..., plugin=path)``).  The reward's contract is in
-``csrc/user_reward.h``.  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
-hashes every csrc source, ``include/dial_mpc.h``, the reward, the dimensions, the flags and ``hipcc --version``.  hipcc
+``csrc/user_reward.h``.  ``control_src`` adds a control law (contract: ``csrc/user_control.h``) in place of BaseEnv's act2joint /
+PD law; such a plugin carries one more kernel (``user_control_kernel``) and exports a second symbol (``CTRL_SYMBOL``).  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
+hashes every csrc source, ``include/dial_mpc.h``, the reward, the control law (when there is one), the dimensions, the flags and ``hipcc --version``.  hipcc
 cross-compiles, so building needs no GPU.
 """
 from __future__ import annotations
@@ -24,6 +26,7 @@ from dial_mpc_amd._lib import _COMMON, _CSRC, _FAST, DialHipError
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOL = "dial_plugin_ops_v1"
+CTRL_SYMBOL = "dial_plugin_ctrl_v1"   # exported only by a plugin built with a control law
 DIM_NAMES = ("nq", "nv", "nu", "nbody", "njnt", "ngeom", "nsite", "ncon", "nlim", "nfri")
 _DIM_MACROS = ("NQ", "NV", "NU", "NB", "NJ", "NG", "NS", "NC", "NL", "NFRI")
 
@@ -93,25 +96,30 @@ def cache_root() -> str:
     return os.environ.get("DIAL_PLUGIN_CACHE", os.path.join(_ROOT, "build", "plugins"))
 
 
-def plugin_key(model, reward_src: str, flags: Sequence[str]) -> str:
+def plugin_key(model, reward_src: str, flags: Sequence[str], control_src: Optional[str] = None) -> str:
     h = hashlib.sha256()
     for p in sorted(glob.glob(os.path.join(_CSRC, "*.h")) + glob.glob(os.path.join(_CSRC, "*.hip"))) + [_abi.HEADER]:
         h.update(os.path.basename(p).encode() + b"\0" + open(p, "rb").read() + b"\0")
     h.update(_read_reward(reward_src).encode() + b"\0")
+    if control_src is not None:
+        h.update(b"control\0" + _read_reward(control_src).encode() + b"\0")
     h.update(dims_header(model).encode() + b"\0")
     h.update(" ".join(flags).encode() + b"\0")
     h.update(subprocess.run([_hipcc(), "--version"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout.encode())
     return h.hexdigest()
 
 
-def build_plugin(model, reward_src: str, flags: Optional[Sequence[str]] = None, verbose: bool = False) -> str:
+def build_plugin(model, reward_src: str, flags: Optional[Sequence[str]] = None, verbose: bool = False,
+                 control_src: Optional[str] = None) -> str:
     """Compile (or find in the cache) the task plugin of `model` with the reward `reward_src` (HIP source text, or the path of a
-    .hip file) -> path of the shared library.  A compile error raises DialHipError with hipcc's own message."""
+    .hip file) and, optionally, the control law `control_src` (the same two forms) -> path of the shared library.  A compile error
+    in either raises DialHipError with hipcc's own message."""
     import fcntl
     check_model(model)
     flags = list(_COMMON + _FAST if flags is None else flags)
     reward = _read_reward(reward_src)
-    key = plugin_key(model, reward, flags)[:24]
+    control = None if control_src is None else _read_reward(control_src)
+    key = plugin_key(model, reward, flags, control)[:24]
     root = cache_root()
     out_dir = os.path.join(root, key)
     out = os.path.join(out_dir, "libdialplugin.so")
@@ -130,8 +138,15 @@ def build_plugin(model, reward_src: str, flags: Optional[Sequence[str]] = None, 
                     f.write("// generated by dial_mpc_amd/plugin.py: the model's compile-time dimensions\n" + dims_header(model))
                 with open(os.path.join(work, "dial_user_reward.hip"), "w") as f:
                     f.write(reward)
+                generated = ["dial_plugin_dims.h", "dial_user_reward.hip"]
+                defs = []
+                if control is not None:
+                    with open(os.path.join(work, "dial_user_control.hip"), "w") as f:
+                        f.write(control)
+                    generated.append("dial_user_control.hip")
+                    defs = ["-DDIAL_PLUGIN_USER_CTRL=1"]
                 obj = os.path.join(work, "plugin.o")
-                cmd = [_hipcc()] + flags + ["-I", work, "-c", "-o", obj, os.path.join(_CSRC, "plugin.hip")]
+                cmd = [_hipcc()] + flags + defs + ["-I", work, "-c", "-o", obj, os.path.join(_CSRC, "plugin.hip")]
                 if verbose:
                     print(" ".join(cmd))
                 r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
@@ -143,7 +158,7 @@ def build_plugin(model, reward_src: str, flags: Optional[Sequence[str]] = None, 
                 if r.returncode != 0:
                     raise DialHipError(f"linking the task plugin failed ({r.returncode}):\n{r.stdout[-4000:]}")
                 os.makedirs(out_dir, exist_ok=True)
-                for name in ("dial_plugin_dims.h", "dial_user_reward.hip"):   # (kept beside the library: what it was built from)
+                for name in generated:   # (kept beside the library: what it was built from)
                     shutil.copy(os.path.join(work, name), os.path.join(out_dir, name))
                 os.replace(so, out)
                 return out

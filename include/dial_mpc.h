@@ -539,7 +539,11 @@ int dial_set_state_trace(dial_ctx* ctx, float* trace, int rows);
  * model's; pyramidal cones only, at most DIAL_KBI_ROWS distinct (solref, solimp) rows.  params:[n_params] (n_params <=
  * DIAL_USER_PARAMS, the rest zero) are the reward's task parameters.  Every entry point above then runs on the context
  * unchanged, except the sharded ones (dial_shard_*), which fail with DIAL_ERR_ARG.  dial_create / dial_create_ex refuse
- * DIAL_TASK_USER.  Fails with DIAL_ERR_ARG / DIAL_ERR_UNSUPPORTED and a message (dial_last_error(NULL)) naming the reason. */
+ * DIAL_TASK_USER.  Fails with DIAL_ERR_ARG / DIAL_ERR_UNSUPPORTED and a message (dial_last_error(NULL)) naming the reason.
+ * A plugin built with a user CONTROL LAW (csrc/user_control.h; plugin.py: build_plugin(control_src=)) exports a second symbol,
+ * dial_plugin_ctrl_v1, next to dial_plugin_ops_v1.  Its kernels run the law in place of act2joint / the PD law and ignore
+ * task->position_control, kp and kd (the law may read kp and kd); dial_user_control below evaluates the law outside a step.  A
+ * plugin without the symbol gives a context without a law: the built-in control, as before. */
 int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task* task, const dial_cfg* cfg, int device,
                        const dial_options* opts, const char* plugin_path, const float* params, int n_params);
 /* New task parameters for a plugin context (no rebuild): params:[n] host floats, n <= DIAL_USER_PARAMS, the rest zero.
@@ -556,6 +560,13 @@ int dial_set_user_params(dial_ctx* ctx, const float* params, int n);
  * or batched env.step of M > rows plans / states fails with DIAL_ERR_ARG.  No synchronisation: launches issued afterwards see
  * the binding. */
 int dial_set_plan_params(dial_ctx* ctx, const float* params, int rows);
+/* The user control law of a task-plugin context, evaluated for n rows in ONE launch: states:[n, dial_state_size(nq,nv)] packed
+ * states, actions:[n,nu] normalised actions -> ctrl_out:[n,nu], the values the actuators would receive if dial_env_step ran from
+ * row g's state with row g's action (the same code, bit for bit).  The law reads row g's qpos, qvel, step counter and user info
+ * slots; with per-plan task parameters bound (dial_set_plan_params) row g reads parameter row g, else the shared parameters.
+ * Nothing is stepped and no state is written.  Fails with DIAL_ERR_ARG and a message when n < 1, when n exceeds the bound
+ * per-plan rows, or when the context has no control law (no task plugin, or a plugin built without one). */
+int dial_user_control(dial_ctx* ctx, const float* states, const float* actions, int n, float* ctrl_out, void* stream);
 
 /* Plant simulator (deploy/dial_sim.py): M plants advanced by K physics steps in ONE launch, each step applying one row of the plan
  * the planner published -- what the reference's dial_sim.py does with MuJoCo's mj_step at sim_dt.  The context is an ordinary

@@ -4,8 +4,11 @@ task forced onto the capacity-dimension kernel (DimsMax, dial_options.force_gene
 cold compile time (empty cache) and its kernels' resource line (tools/isa/disasm_lib.py).  Writes a markdown report.
 --plan-params: instead, grouped reverse_once_batch_rng of the example plugin at M plans (--plans, default 4 and 32), the shared task
 parameters against bound per-plan rows (dial_set_plan_params), alternating.
+--control-law: instead, reverse_once of the example reward's plugin WITHOUT a control law against the same plugin WITH BaseEnv's
+torque law restated as a user law (examples/custom_env/base_pd_law.hip), alternating; the difference next to the spread of the
+no-law plugin's own rounds, and both plugins' kernel resource lines.
 
-usage: bench_custom_env.py <out.md> [--iters 200] [--rounds 3] [--plan-params [--plans 4 32]]"""
+usage: bench_custom_env.py <out.md> [--iters 200] [--rounds 3] [--plan-params [--plans 4 32]] [--control-law]"""
 import argparse
 import importlib
 import os
@@ -90,6 +93,40 @@ def plan_params_report(a, env, dc, cfg):
     return lines
 
 
+def _isa_notes(path, tag):
+    return subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa", "disasm_lib.py"), path, os.path.join(tempfile.gettempdir(), tag),
+                           "--notes-only"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout.replace(ROOT + os.sep, "").strip()
+
+
+def control_law_report(a, env, dc, cfg):
+    import torch
+    from dial_mpc_amd import _lib, plugin
+    law = os.path.join(ROOT, "dial_mpc_amd", "examples", "custom_env", "base_pd_law.hip")
+    paths = {"no law (built-in control)": env.plugin_path(),
+             "restated PD law (base_pd_law.hip)": plugin.build_plugin(env.sys.model, env.reward_source(), control_src=law)}
+    ctxs = {k: _lib.Context(env.make_model(), env.make_task(), cfg, plugin=p, user_params=env.user_param_vector()) for k, p in paths.items()}
+    res = {k: [] for k in ctxs}
+    for _ in range(a.rounds):   # alternating, so that clock / power drift hits both alike
+        for k, ctx in ctxs.items():
+            s0, _, _ = ctx.env_reset(torch.as_tensor(env._init_q, dtype=torch.float32, device="cuda"), torch.zeros(ctx.nv, device="cuda"))
+            res[k].append(_ms_per_call(ctx, s0, dc, a.iters))
+    base, with_law = (np.asarray(v) for v in res.values())
+    lines = ["# User control laws: the plugin with a restated PD law against the plugin without a law", "",
+             f"reverse_once (lean: mean action only), go2_height_walk reward, Go2 model, N = {dc.Nsample}, H = {dc.Hsample}, Hnode = {dc.Hnode}; "
+             f"{a.iters} calls per measurement, {a.rounds} alternating rounds (median; all rounds listed).  The baseline is the no-law plugin "
+             "of the same run.", "",
+             "| plugin | ms per reverse_once (median) | min | max | rounds |", "|---|---|---|---|---|"]
+    for k, v in res.items():
+        lines.append(f"| {k} | {np.median(v):.4f} | {min(v):.4f} | {max(v):.4f} | {', '.join(f'{x:.4f}' for x in v)} |")
+    diff, spread = float(np.median(with_law) - np.median(base)), float(base.max() - base.min())
+    lines += ["", f"Difference of the medians (law - no law): {diff * 1e3:+.2f} us ({100 * diff / np.median(base):+.2f} %); spread (max - min) of "
+              f"the no-law plugin's own rounds: {spread * 1e3:.2f} us; per-round differences: "
+              f"{', '.join(f'{1e3 * (x - y):+.2f}' for x, y in zip(with_law, base))} us.", ""]
+    for k, p in paths.items():
+        lines += [f"Kernels of the plugin, {k} (tools/isa/disasm_lib.py --notes-only):", "", "```", _isa_notes(p, "isa_" + ("law" if "restated" in k else "nolaw")), "```", ""]
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out")
@@ -97,6 +134,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--plan-params", action="store_true", help="measure shared against per-plan task parameters instead")
     ap.add_argument("--plans", type=int, nargs="+", default=[4, 32])
+    ap.add_argument("--control-law", action="store_true", help="measure the plugin without a control law against one with the restated PD law instead")
     a = ap.parse_args()
     import torch
     from dial_mpc_amd import _lib, plugin
@@ -105,8 +143,8 @@ def main():
     d = yaml.safe_load(open(os.path.join(ROOT, "dial_mpc_amd", "examples", "custom_env", "go2_height_walk.yaml")))
     d["Nsample"], d["Hsample"] = 2048, 16
     dc, _, env = load_dial_and_env(d)
-    if a.plan_params:
-        lines = plan_params_report(a, env, dc, make_cfg(dc))
+    if a.plan_params or a.control_law:
+        lines = (plan_params_report if a.plan_params else control_law_report)(a, env, dc, make_cfg(dc))
         open(a.out, "w").write("\n".join(lines) + "\n")
         print("\n".join(lines))
         return
