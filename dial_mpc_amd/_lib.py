@@ -206,6 +206,11 @@ def load(path: Optional[str] = None):
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack user control laws)
             raise
     try:
+        lib.dial_set_user_table.argtypes = [vp, fp, ci, ci, ci, ci]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack the reference table)
+            raise
+    try:
         lib.dial_plant_step.argtypes = [vp, fp, fp, fp, fp, ci, ctypes.c_double, ctypes.c_double, ci, ci, fp, ci, vp]
     except AttributeError:
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack the plant simulator)
@@ -236,7 +241,8 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
             "dial_shard_ybar_gathered", "dial_shard_ybar_gathered_rng", "dial_shard_reduce_gathered", "dial_shift", "dial_env_step", "dial_env_reset", "dial_env_reset_batch",
             "dial_status", "dial_set_timing", "dial_get_rollout_ms", "dial_abi_sizes",
             "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch",
-            "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params", "dial_plant_step", "dial_user_control")
+            "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params", "dial_plant_step", "dial_user_control",
+            "dial_set_user_table")
 
 # dial_plant_step flags (include/dial_mpc.h)
 PLANT_CTRL, PLANT_PD, PLANT_HOLD_FIRST = (_abi.MACROS[k] for k in ("DIAL_PLANT_CTRL", "DIAL_PLANT_PD", "DIAL_PLANT_HOLD_FIRST"))
@@ -258,6 +264,44 @@ def plan_param_rows(rows) -> np.ndarray:
     return out
 
 
+TABLE_MODES = {"clamp": _abi.MACROS["DIAL_TABLE_CLAMP"], "wrap": _abi.MACROS["DIAL_TABLE_WRAP"]}
+TABLE_MAX_ROWS = 1 << 24
+
+
+def table_mode(mode) -> int:
+    """"clamp" / "wrap" (or the DIAL_TABLE_* value) -> the mode dial_set_user_table takes.  Raises ValueError on anything else."""
+    if isinstance(mode, str) and mode in TABLE_MODES:
+        return TABLE_MODES[mode]
+    if not isinstance(mode, (str, bool)) and mode in TABLE_MODES.values():
+        return int(mode)
+    raise ValueError(f"reference table mode {mode!r}; one of {sorted(TABLE_MODES)}")
+
+
+def check_user_table(shape, dtype=None) -> None:
+    """Raise ValueError unless `shape` (and `dtype`, where given) is a reference table's: [rows, cols] float32 with
+    1 <= rows <= 1 << 24 and 1 <= cols <= DIAL_USER_TABLE_COLS."""
+    cap = _abi.MACROS["DIAL_USER_TABLE_COLS"]
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != 2:
+        raise ValueError(f"a reference table is [rows, cols]; got shape {shape}")
+    if not 1 <= shape[0] <= TABLE_MAX_ROWS:
+        raise ValueError(f"a reference table has 1 .. {TABLE_MAX_ROWS} rows; got shape {shape}")
+    if not 1 <= shape[1] <= cap:
+        raise ValueError(f"a reference table has 1 .. DIAL_USER_TABLE_COLS = {cap} columns; got shape {shape}")
+    if dtype is not None and str(dtype) != "torch.float32" and (str(dtype).startswith("torch.") or np.dtype(dtype) != np.float32):
+        raise ValueError(f"a reference table is float32; got {dtype}")
+
+
+def user_table_array(table) -> np.ndarray:
+    """A host table (array or nested list) as dial_set_user_table takes it: float32 [rows, cols], C-contiguous.  Floating-point and
+    integer input is converted; anything else, another rank or size raises ValueError."""
+    a = np.asarray(table)
+    if a.dtype.kind not in "fiu":
+        raise ValueError(f"a reference table holds floats; got dtype {a.dtype}")
+    check_user_table(a.shape)
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
 def _ptr(t) -> Optional[int]:
     if t is None:
         return None
@@ -275,13 +319,15 @@ class Context:
 
     def __init__(self, model: "_abi.DialModel", task: "_abi.DialTask", cfg: Optional["_abi.DialCfg"],
                  device: Optional[int] = None, n_local_cap: Optional[int] = None, lib_path: Optional[str] = None,
-                 options: Optional[dict] = None, plugin: Optional[str] = None, user_params=None):
+                 options: Optional[dict] = None, plugin: Optional[str] = None, user_params=None,
+                 user_table=None, table_row0: int = 0, table_mode: str = "clamp"):
         """n_local_cap: size the rollout scratch for that many local samples (one rank of a sharded run).
         lib_path: another build of the library (measurement variants, e.g. libdialhip_ieee.so).
         options: fields of `dial_options` (include/dial_mpc.h) -- launch-shape / measurement switches, e.g.
         dict(no_queue=1); none of them changes a result bit.  The library itself reads no environment variables.
         plugin: path of a task plugin (dial_mpc_amd/plugin.py: build_plugin) whose kernels serve this context (task.kind =
-        DIAL_TASK_USER; dial_create_plugin), user_params its float task parameters (<= DIAL_USER_PARAMS; set_user_params)."""
+        DIAL_TASK_USER; dial_create_plugin), user_params its float task parameters (<= DIAL_USER_PARAMS; set_user_params),
+        user_table / table_row0 / table_mode its reference table (set_user_table)."""
         import torch
         self.lib = load(lib_path)
         if not torch.cuda.is_available():
@@ -300,6 +346,11 @@ class Context:
             raise ValueError(f"unknown dial_options fields: {sorted(unknown)}")
         opts = _abi.fill(_abi.DialOptions(), self.options)
         self.plugin = plugin
+        self._user_table = None
+        if user_table is not None and plugin is None:
+            raise DialHipError("user_table: the reference table is a task plugin's (plugin=)")
+        if user_table is not None and not hasattr(user_table, "is_cuda"):
+            user_table = user_table_array(user_table)   # (refuse a bad table before anything is created)
         if plugin is not None:
             if n_local_cap is not None:
                 raise DialHipError("task-plugin contexts cannot be sharded (n_local_cap)")
@@ -311,6 +362,8 @@ class Context:
             if rc != 0:
                 raise DialHipError(f"dial_create_plugin failed ({rc}): {self.lib.dial_last_error(None).decode()}")
             self.h = h
+            if user_table is not None:
+                self.set_user_table(user_table, table_row0, table_mode)
             return
         rc = self.lib.dial_create_ex(ctypes.byref(h), ctypes.addressof(model), ctypes.addressof(task),
                                      ctypes.addressof(cfg) if cfg is not None else None, self.device,
@@ -351,6 +404,31 @@ class Context:
             dev = torch.as_tensor(plan_param_rows(rows), device=self.torch_device)
         self._check(self.lib.dial_set_plan_params(self.h, dev.data_ptr(), int(dev.shape[0])), "dial_set_plan_params")
         self._plan_params = dev
+        return dev
+
+    def set_user_table(self, table, row0: int = 0, mode="clamp"):
+        """The reference table of a task-plugin context (dial_set_user_table): `table` [rows, cols <= DIAL_USER_TABLE_COLS], a host
+        array (copied to the device) or a contiguous float32 device tensor (bound as it is).  Every control step hands the reward
+        and the control law row clamp-or-wrap(step counter + row0).  Returns the bound device tensor: it stays alive while bound and
+        may be rewritten in place between launches without a new call.  None unbinds.  Synchronises the device."""
+        import torch
+        m = table_mode(mode)
+        if table is None:
+            self._check(self.lib.dial_set_user_table(self.h, None, 0, 0, 0, m), "dial_set_user_table")
+            self._user_table = None
+            return None
+        if isinstance(table, torch.Tensor) and table.is_cuda:
+            check_user_table(table.shape, table.dtype)
+            if table.device != self.torch_device or not table.is_contiguous():
+                raise ValueError("a device reference table must be contiguous and on the context's device")
+            dev = table
+        else:
+            if isinstance(table, torch.Tensor):
+                table = table.detach().numpy()
+            dev = torch.as_tensor(user_table_array(table), device=self.torch_device)
+        self._check(self.lib.dial_set_user_table(self.h, dev.data_ptr(), int(dev.shape[0]), int(dev.shape[1]), int(row0), m),
+                    "dial_set_user_table")
+        self._user_table = dev
         return dev
 
     def user_control(self, states, actions):

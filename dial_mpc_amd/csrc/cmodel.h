@@ -224,9 +224,17 @@ struct CModelUserCtrl<D, true> {
 };
 template <class D, bool USER = D::user>
 struct CModelUser {};
+// The reference table (dial_set_user_table): the binding, written by the host (plugin_ops.h: set_table), and the words the kernels
+// write in their STAGED copy of the constants -- the two-row ring that holds the control step's row and the next one
+// (rollout_driver.h) and which half / which row the step's reward and law read.  table_rows == 0: no table bound.
 template <class D>
 struct CModelUser<D, true> : CModelUserCtrl<D> {
   float user_params[DIAL_USER_PARAMS];
+  const float* table;                                // [table_rows][table_cols], caller-owned device memory
+  int32_t table_rows, table_cols, table_row0, table_mode;
+  int32_t table_half, table_cur;                     // (staged copy only) the ring's half of this control step, its row index
+  int32_t table_nidx, table_nr;                      // (staged copy only) the row in flight: its index, its step counter + row0
+  float table_ring[2][DIAL_USER_TABLE_COLS];         // (staged copy only)
 };
 
 // Everything one env.step reads that is constant across samples and steps.

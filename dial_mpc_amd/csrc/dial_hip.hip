@@ -349,6 +349,7 @@ struct dial_ctx {
                               // 7 a task plugin's instantiation (dial_create_plugin: `plug`)
   const dial_plugin_ops* plug = nullptr;   // inst 7: the plugin's host functions (the library stays loaded for the process)
   const dial_plugin_ctrl* plug_ctrl = nullptr;   // inst 7: the plugin's user control law (dial_user_control), nullptr when it has none
+  const dial_plugin_table* plug_table = nullptr; // inst 7: the plugin's reference-table function (dial_set_user_table), nullptr: an older plugin
   std::vector<char> plug_cm;               // inst 7: host copy of the constants (dial_set_user_params rewrites the parameters)
   const float* plan_params = nullptr;      // inst 7: per-plan task parameters (dial_set_plan_params), caller-owned device rows ...
   int plan_rows = 0;                       // ... [plan_rows, DIAL_USER_PARAMS]; nullptr: every launch reads the shared ones
@@ -503,8 +504,19 @@ int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task*
         ctl->nu != model->nu)
       return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's control-law table was built against another version of the library (ABI mismatch; rebuild it)");
   }
+  // the reference table's function: a third symbol, absent from a plugin built before the table existed
+  const dial_plugin_table* tab = nullptr;
+  if (dial_plugin_table_entry tentry = (dial_plugin_table_entry)dlsym(h, DIAL_PLUGIN_TABLE_SYMBOL)) {
+    tab = tentry();
+    if (!tab) return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + plugin_path + ": " DIAL_PLUGIN_TABLE_SYMBOL " returned no table");
+    if (tab->version != DIAL_PLUGIN_TABLE_VERSION)
+      return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: stale plugin: its reference-table entry reports version ") + std::to_string(tab->version) +
+                                         ", the library needs version " + std::to_string(DIAL_PLUGIN_TABLE_VERSION) + " (rebuild it from the current sources)");
+    if (tab->cmodel_bytes != ops->cmodel_bytes || tab->sizeof_reward_in != sizeof(DialRewardIn) || tab->sizeof_control_in != sizeof(DialControlIn))
+      return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's reference-table entry was built against another version of the library (ABI mismatch; rebuild it)");
+  }
   const int rc = create_impl(out, model, task, cfg, device, -1, opts, ops, params, n_params);
-  if (rc == DIAL_OK) (*out)->plug_ctrl = ctl;
+  if (rc == DIAL_OK) { (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; }
   return rc;
 }
 
@@ -527,6 +539,26 @@ int dial_set_user_params(dial_ctx* ctx, const float* params, int n) {
   if (!ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_set_user_params: the context has no task plugin (dial_create_plugin)");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->plug->set_params(ctx->plug_cm.data(), params, n);
+  HIP_TRY(ctx, hipDeviceSynchronize());   // (launches in flight read the constants)
+  HIP_TRY(ctx, hipMemcpy(ctx->dcm, ctx->plug_cm.data(), ctx->plug->cmodel_bytes, hipMemcpyHostToDevice));
+  return DIAL_OK;
+}
+
+int dial_set_user_table(dial_ctx* ctx, const float* table, int rows, int cols, int row0, int mode) {
+  if (!ctx) return fail(ctx, DIAL_ERR_ARG, "dial_set_user_table: null context");
+  if (!ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_set_user_table: the context has no task plugin (dial_create_plugin): the reference table is a task plugin's");
+  if (!table && rows != 0) return fail(ctx, DIAL_ERR_ARG, "dial_set_user_table: a null table with rows = " + std::to_string(rows) + " (NULL with rows = 0 unbinds)");
+  if (table && (rows < 1 || rows > (1 << 24)))
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_user_table: rows = " + std::to_string(rows) + " is outside 1 .. 1 << 24");
+  if (table && (cols < 1 || cols > DIAL_USER_TABLE_COLS))
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_user_table: cols = " + std::to_string(cols) + " is outside 1 .. DIAL_USER_TABLE_COLS");
+  if (mode != DIAL_TABLE_CLAMP && mode != DIAL_TABLE_WRAP)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_user_table: unknown mode " + std::to_string(mode) + " (DIAL_TABLE_CLAMP or DIAL_TABLE_WRAP)");
+  if (!ctx->plug_table)
+    return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_set_user_table: the context's task plugin does not export " DIAL_PLUGIN_TABLE_SYMBOL
+                                           " (built before the reference table existed; rebuild it)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->plug_table->set_table(ctx->plug_cm.data(), table, rows, cols, row0, mode);
   HIP_TRY(ctx, hipDeviceSynchronize());   // (launches in flight read the constants)
   HIP_TRY(ctx, hipMemcpy(ctx->dcm, ctx->plug_cm.data(), ctx->plug->cmodel_bytes, hipMemcpyHostToDevice));
   return DIAL_OK;

@@ -6,6 +6,7 @@
 // and, for a plugin with a user control law (-DDIAL_PLUGIN_USER_CTRL=1), a third:
 //   dial_user_control.hip the user's definition of dial_user_control (user_control.h states the contract)
 // Such a plugin carries one more kernel, user_control_kernel, and exports a second table (plugin_ops.h: dial_plugin_ctrl).
+// Every plugin exports a third, dial_plugin_table (the reference table of dial_set_user_table: host code only, no kernel).
 #include "plugin_ops.h"
 #include "dial_plugin_dims.h"
 #include "dial_user_reward.hip"
@@ -34,6 +35,14 @@ template __global__ void env_reset_kernel<DimsPlugin>(const CModel<DimsPlugin>*,
 extern "C" __attribute__((visibility("default"))) const dial_plugin_ops* dial_plugin_ops_v1(void) {
   return PluginOps<DimsPlugin, DIAL_PLUGIN_WPB>::table();
 }
+
+// the reference table's host function (plugin_ops.h: dial_plugin_table): every plugin exports it, with or without a law
+// (-DDIAL_PLUGIN_NO_TABLE: a plugin as the sources before the table built it -- the tests' stand-in for an older plugin)
+#ifndef DIAL_PLUGIN_NO_TABLE
+extern "C" __attribute__((visibility("default"))) const dial_plugin_table* dial_plugin_table_v1(void) {
+  return PluginTable<DimsPlugin>::table();
+}
+#endif
 
 #if DIAL_PLUGIN_USER_CTRL
 template __global__ void user_control_kernel<DimsPlugin>(const CModel<DimsPlugin>*, const float*, const float*, float*, const float*);

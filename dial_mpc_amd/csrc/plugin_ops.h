@@ -81,7 +81,14 @@ user_control_kernel(const CModel<D>* __restrict__ gm, const float* __restrict__ 
   const float* const st = states + (size_t)g * (D::NQ + 2 * D::NV + DIAL_INFO_N);
   const float* const info = st + D::NQ + 2 * D::NV;
   const float* const params = plan_params ? plan_params + (size_t)g * DIAL_USER_PARAMS : gm->user_params;
-  const DialControlIn in = dial::control_in(gm, info[DIAL_INFO_STEP], st, st + D::NQ, actions + (size_t)g * D::NU);
+  // the reference table: nothing is staged here either -- the row of this state's counter straight from global memory
+  const float* trow = nullptr;
+  int tindex = 0;
+  if (gm->table_rows > 0) {
+    tindex = dial::table_row_index((int)info[DIAL_INFO_STEP], gm->table_row0, gm->table_rows, gm->table_mode);
+    trow = gm->table + (size_t)tindex * gm->table_cols;
+  }
+  const DialControlIn in = dial::control_in(gm, info[DIAL_INFO_STEP], st, st + D::NQ, actions + (size_t)g * D::NU, trow, tindex);
   ctrl_out[(size_t)g * D::NU + a] = dial_user_control(in, a, params, info + DIAL_INFO_USER);
 }
 
@@ -95,6 +102,49 @@ struct PluginCtrl {
   static const dial_plugin_ctrl* table() {
     static const dial_plugin_ctrl ctl = {DIAL_PLUGIN_CTRL_VERSION, D::NQ, D::NV, D::NU, sizeof(CModel<D>), sizeof(DialControlIn), &user_control};
     return &ctl;
+  }
+};
+
+// The reference table (dial_set_user_table): a THIRD optional table under a third symbol, exported by every plugin built from
+// sources that know the table, with or without a law; dial_plugin_ops, dial_plugin_ctrl and their versions stay as they are.  The
+// binding lives in the plugin's constants (cmodel.h: CModelUser), so the kernels take no new argument: set_table writes it into the
+// host copy, which dial_set_user_table uploads.
+#ifndef DIAL_PLUGIN_TABLE_VERSION   // (overridable on a plugin's command line: the tests build one that reports another version)
+#define DIAL_PLUGIN_TABLE_VERSION 1
+#endif
+#define DIAL_PLUGIN_TABLE_SYMBOL "dial_plugin_table_v1"
+struct dial_plugin_table {
+  int version;                     // DIAL_PLUGIN_TABLE_VERSION
+  size_t cmodel_bytes;             // sizeof(CModel<D>): the same constants as dial_plugin_ops' (ABI check)
+  size_t sizeof_reward_in, sizeof_control_in;   // sizeof(DialRewardIn), sizeof(DialControlIn)
+  // bind dev_table [rows, cols] (device memory) with offset row0 and mode DIAL_TABLE_*, or unbind (nullptr, rows 0); the caller
+  // (dial_set_user_table) has validated the arguments
+  void (*set_table)(void* host_cm, const float* dev_table, int rows, int cols, int row0, int mode);
+};
+typedef const dial_plugin_table* (*dial_plugin_table_entry)(void);
+
+template <class D>
+struct PluginTable {
+  static void set_table(void* host_cm, const float* dev_table, int rows, int cols, int row0, int mode) {
+    CModel<D>* c = (CModel<D>*)host_cm;
+    const bool on = dev_table && rows > 0;
+    // row0 as the device adds it to a step counter (rollout_body.h: table_row_index): no overflow for counters within +-2^24
+    int r0 = 0;
+    if (on && mode == DIAL_TABLE_WRAP) r0 = ((row0 % rows) + rows) % rows;
+    else if (on) r0 = row0 < -(1 << 30) ? -(1 << 30) : (row0 > (1 << 30) ? (1 << 30) : row0);
+    c->table = on ? dev_table : nullptr;
+    c->table_rows = on ? rows : 0;
+    c->table_cols = on ? cols : 0;
+    c->table_row0 = r0;
+    c->table_mode = on ? mode : 0;
+    c->table_half = 0;
+    c->table_cur = 0;
+    c->table_nidx = 0;
+    c->table_nr = 0;
+  }
+  static const dial_plugin_table* table() {
+    static const dial_plugin_table tab = {DIAL_PLUGIN_TABLE_VERSION, sizeof(CModel<D>), sizeof(DialRewardIn), sizeof(DialControlIn), &set_table};
+    return &tab;
   }
 };
 

@@ -1779,11 +1779,27 @@ DIAL_DEV float act2joint(const M* m, float act, int a) {
   float jt = (m->joint_range[a][0] + m->joint_offset[a]) + an * (m->joint_range[a][1] - m->joint_range[a][0]);
   return dm::clip(jt, m->phys_range[a][0], m->phys_range[a][1]);
 }
-// what a user control law reads (user_control.h), from the constants `m` and the state / action arrays of the caller
+// The reference table of a task plugin (dial_set_user_table; user_reward.h states the rule): the row of the control step whose
+// step counter is `step`.  row0 arrives prepared by the host (PluginOps::set_table): reduced into [0, rows) under DIAL_TABLE_WRAP,
+// limited to +-2^30 under DIAL_TABLE_CLAMP, so that step + row0 cannot overflow for any counter a float holds exactly.
+DIAL_DEV int table_row_index(int step, int row0, int rows, int mode) {
+  const int r = step + row0;
+  if (mode == DIAL_TABLE_WRAP) { const int q = r % rows; return q < 0 ? q + rows : q; }
+  return r < 0 ? 0 : (r > rows - 1 ? rows - 1 : r);
+}
+// the row after row `idx` when the step counter advances by one, without a division; r_next: the next step's counter + row0
+DIAL_DEV int table_next_index(int idx, int r_next, int rows, int mode) {
+  if (mode == DIAL_TABLE_WRAP) return idx + 1 == rows ? 0 : idx + 1;
+  return r_next < 0 ? 0 : (r_next > rows - 1 ? rows - 1 : r_next);
+}
+// what a user control law reads (user_control.h), from the constants `m` and the state / action arrays of the caller; trow /
+// tindex: the step's row of the reference table where the caller holds it (the ring in LDS, or global memory), nullptr without one
 template <class M>
-DIAL_DEV DialControlIn control_in(const M* m, float step, const float* qpos, const float* qvel, const float* act) {
+DIAL_DEV DialControlIn control_in(const M* m, float step, const float* qpos, const float* qvel, const float* act, const float* trow,
+                                  int tindex) {
   return DialControlIn{dim_nq(m), dim_nv(m), dim_nu(m), step, m->dt, qpos, qvel, act, m->act_qposadr, m->act_dofadr, m->action_scale,
-                       m->kp, m->kd, &m->joint_range[0][0], &m->phys_range[0][0], &m->tau_range[0][0], m->joint_offset};
+                       m->kp, m->kd, &m->joint_range[0][0], &m->phys_range[0][0], &m->tau_range[0][0], m->joint_offset,
+                       trow, tindex, m->table, m->table_rows, m->table_cols};
 }
 // get_foot_step for foot f at the (pre-increment) step counter `step` (function_utils.py:18-43)
 template <class M>
@@ -1805,8 +1821,11 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
   } else if constexpr (M::D::user_ctrl) {
     // a task plugin's user control law (user_control.h) in place of act2joint / the PD law: lane a evaluates actuator a from the state
     // the step starts from; position_control, kp and kd decide nothing here (a plugin has no gait clock: nothing else in this phase)
+    // (the step's table row: staged in the ring by the caller before the step -- rollout_driver.h, env_step_kernel)
     w.items(nu, [&](int a) {
-      const DialControlIn in = control_in(m, s.info[DIAL_INFO_STEP], s.qpos, s.qvel, s.act);
+      const bool tab = m->table_rows > 0;
+      const DialControlIn in = control_in(m, s.info[DIAL_INFO_STEP], s.qpos, s.qvel, s.act, tab ? m->table_ring[m->table_half] : nullptr,
+                                          tab ? m->table_cur : 0);
       const float c = dial_user_control(in, a, m->user_params, s.info + DIAL_INFO_USER);
       s.ctrl[a] = c;
       s.info[DIAL_INFO_LAST_CTRL + a] = c;
@@ -1844,8 +1863,10 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
     w.items(1, [&](int) {
       float* info = s.info;
       const float step = info[DIAL_INFO_STEP];
+      const bool tab = m->table_rows > 0;   // (the row the law of this step saw: the ring's current half)
       const DialRewardIn in{dim_nq(m), dim_nv(m), nu, dim_nb(m), dim_ns(m), dim_nc(m), step, m->dt,
-                            s.qpos, s.qvel, s.xpos, s.xquat, s.spos, s.cdist, s.cpos, s.ctrl, s.act};
+                            s.qpos, s.qvel, s.xpos, s.xquat, s.spos, s.cdist, s.cpos, s.ctrl, s.act,
+                            tab ? m->table_ring[m->table_half] : nullptr, tab ? m->table_cur : 0, m->table, m->table_rows, m->table_cols};
       const float reward = dial_user_reward(in, m->user_params, info + DIAL_INFO_USER);
       if (FULL_INFO) info[DIAL_INFO_DONE] = 0.f;
       info[DIAL_INFO_STEP] = step + 1.f;

@@ -40,6 +40,27 @@ DIAL_DEV void store_state(W& w, const M* m, const Ws& s, float* state) {
   });
 }
 
+#ifndef DIAL_EMU
+// The reference table of a task plugin (dial_set_user_table).  Rows reach the reward and the law through a two-row ring in the
+// wavefront's staged constants (CModelUser::table_ring): a global load on the reward lane, after the physics, would put an L2 round
+// trip on the wavefront's dependence chain in every step, and a law reads its row at the very top of the step.  So lanes 0 .. cols - 1
+// load the NEXT step's row at the top of a control step (one coalesced vector load) and store it into the ring's other half where
+// that step begins -- the first point that waits for the load; the step's physics lies in between.
+// table_fetch: the load of the row with index `idx` (a wave-uniform value), one float per lane.
+template <class M>
+DIAL_DEV float table_fetch(const M* m, int lane, int idx, int cols) {
+  return lane < cols ? m->table[(size_t)idx * cols + lane] : 0.f;
+}
+// table_publish: `v` (the fetched row `idx`) into half `half` of the ring, which the step's law and reward then read
+template <class W, class M>
+DIAL_DEV void table_publish(W& w, const M* m, int half, int idx, int cols, float v) {
+  M* const c = const_cast<M*>(m);   // (the wavefront's own staged copy)
+  if (w.lane < cols) c->table_ring[half][w.lane] = v;
+  if (w.lane == 0) { c->table_half = half; c->table_cur = idx; }
+  w.sync();
+}
+#endif
+
 #ifndef DIAL_RSUM_FP64
 #define DIAL_RSUM_FP64 1   // A/B switch: 0 = the fp32 running reward sum of rounds 1-5
 #endif
@@ -201,6 +222,25 @@ DIAL_DEV void rollout_sample(W& w, const M* m, const dial_task* tg, const dial_c
     rsum = load_sum(rbuf + nstate);
   }
   if (relay >= 0 && io.relay_stride == 0) w.hold_priority(3);   // (the lone relay rollout; the sliced queue keeps the fair sharing)
+  // the reference table (task plugins): this rollout item's / relay piece's first row, loaded here in the prologue once the state
+  // (and with it the step counter) is in the workspace -- load_state ends with the wavefront's LDS fence (Wave::items), so the counter
+  // is readable here; every queue item and every relay piece passes here.  tnext: the row in flight, one float per lane; its index
+  // and its step counter + row0 (what the clamp rule clamps) live next to the ring in the staged constants (table_nidx, table_nr),
+  // not in registers: the kernel already spills scalar registers, and a context without a table (trows == 0: one uniform branch
+  // per step, nothing loaded) should carry one scalar through the step loop, not four.
+  int trows = 0;
+  float tnext = 0.f;
+  (void)tnext;
+  if constexpr (M::D::user) {
+    trows = __builtin_amdgcn_readfirstlane(m->table_rows);
+    if (trows > 0) {
+      M* const c = const_cast<M*>(m);   // (the wavefront's own staged copy)
+      const int step = (int)s.info[DIAL_INFO_STEP], idx = table_row_index(step, m->table_row0, trows, m->table_mode);
+      tnext = table_fetch(m, w.lane, idx, m->table_cols);
+      if (w.lane == 0) { c->table_nidx = idx; c->table_nr = step + m->table_row0; }
+      w.sync();
+    }
+  }
 #endif
   if constexpr (PRE) {
     // the gait clock of this (piece of the) rollout: step counter of control step t = the counter now + (t - st_begin), exactly
@@ -246,6 +286,24 @@ DIAL_DEV void rollout_sample(W& w, const M* m, const dial_task* tg, const dial_c
     // physics frame: 0 spilled VGPRs, 0 B of scratch).  (The dimension-specialised register-solver kernels have no spills to cure: there the hoisted addresses pay for
     // themselves -- measured 5 % slower with the laundering, DESIGN.md.)
     if (w.launder) { asm volatile("" : "+v"(w.lane)); w.lane_r = w.lane; }   // (and once per physics frame: rollout_body.h env_step)
+    if constexpr (M::D::user) {
+      // the step's table row into the ring's half st & 1 (the wait for the load issued one step ago), then the load of the next
+      // step's row.  A mean-trajectory pass (mean_now) runs control step `helper` right after the own step `helper`, from a state
+      // with the same counter -- both rollouts start from io.state: the interleaved mean trajectory belongs to one-plan launches
+      // (dial_hip.hip sets io.mean_inline only with io.plan_rollouts == 0) -- so its row is still the published one, and the row
+      // fetched for the own step helper + 1 stays in flight.
+      if (trows > 0 && !mean_now) {
+        const int idx = m->table_nidx, cols = m->table_cols;
+        table_publish(w, m, st & 1, idx, cols, tnext);
+        if (st + 1 < st_end) {
+          M* const c = const_cast<M*>(m);
+          const int r = m->table_nr + 1, nidx = table_next_index(idx, r, trows, m->table_mode);
+          tnext = table_fetch(m, w.lane, nidx, cols);
+          w.sync();   // (every lane has read table_nr before lane 0 rewrites it)
+          if (w.lane == 0) { c->table_nidx = nidx; c->table_nr = r; }
+        }
+      }
+    }
 #endif
     // K2: node2u as the constant linear map W (dial_core.py:92-95,117)
     if constexpr (!PRE) {

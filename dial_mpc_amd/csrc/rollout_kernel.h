@@ -220,6 +220,12 @@ env_step_kernel(const CModel<D>* __restrict__ gm, const dial_task* __restrict__ 
       float* const up = const_cast<float*>(m->user_params);
       w.items(DIAL_USER_PARAMS, [&](int k) { up[k] = plan_params[(size_t)b * DIAL_USER_PARAMS + k]; });
     }
+    // the reference table (dial_set_user_table): the one row of this step, picked by state b's own counter, into the ring
+    if (m->table_rows > 0) {
+      const int step = __builtin_amdgcn_readfirstlane((int)state[(size_t)b * (nq + 2 * nv + DIAL_INFO_N) + nq + 2 * nv + DIAL_INFO_STEP]);
+      const int idx = dial::table_row_index(step, m->table_row0, m->table_rows, m->table_mode), cols = m->table_cols;
+      dial::table_publish(w, m, 0, idx, cols, dial::table_fetch(m, w.lane, idx, cols));
+    }
   }
   dial::env_step_single(w, m, tg, s, state + (size_t)b * (nq + 2 * nv + DIAL_INFO_N), action + (size_t)b * nu,
                         xpos_out ? xpos_out + (size_t)b * nb1 * 3 : nullptr, xquat_out ? xquat_out + (size_t)b * nb1 * 4 : nullptr,

@@ -24,6 +24,10 @@
 //   sampling range), phys_range [nu][2] (the joint limits), tau_range [nu][2] (the actuators' ctrlrange), joint_offset [nu]
 //   params:    the DIAL_USER_PARAMS task parameters the reward gets too (the per-plan row where rows are bound)
 //   info_user: READ-ONLY view of the DIAL_INFO_USER_N slots as the reward left them on the previous step; zero after env.reset
+//   the reference table (dial_set_user_table; optional), exactly as the reward of the same control step sees it (user_reward.h
+//   states the index rule): row [table_cols] the step's row, picked by `step`; row_index; table / table_rows / table_cols the whole
+//   table in global memory for look-ahead.  Unlike poses the row IS valid at control time -- it depends on the step counter only,
+//   not on forward().  With no table bound: table == row == nullptr, table_rows == table_cols == 0, row_index == 0.
 // What it does NOT see, and why: body / site poses (xpos, xquat, spos), contact distances and points, velocities of bodies.  They
 // are results of forward(), and at control time they are not valid: the first step after a state was loaded (the start of every
 // rollout, every env.step) has not run forward() yet, so the workspace holds either nothing or another sample's values.  A law that
@@ -47,6 +51,11 @@ struct DialControlIn {
   const float *kp, *kd;
   const float *joint_range, *phys_range, *tau_range;   // [nu][2]: lo, hi
   const float* joint_offset;
+  // (appended: control sources that predate the reference table compile unchanged)
+  const float* row;                                    // the step's row of the reference table [table_cols], nullptr without one
+  int row_index;
+  const float* table;                                  // [table_rows][table_cols] in global memory, or nullptr
+  int table_rows, table_cols;
 };
 
 // defined by the plugin's control source (the plugin's translation unit only; no kernel of libdialhip.so calls it)

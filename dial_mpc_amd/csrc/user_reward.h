@@ -29,6 +29,18 @@
 //   params:    the DIAL_USER_PARAMS task parameters (dial_create_plugin / dial_set_user_params; unset entries are zero).
 //   info_user: DIAL_INFO_USER_N read / write floats of the env info (slots DIAL_INFO_USER ...).  Zero after env.reset; they persist
 //              from step to step of a rollout and across env.step, like upstream's state.info.
+//   the reference table (dial_set_user_table; optional): one device-resident float table [table_rows][table_cols] per context, data
+//   that changes from step to step -- a motion clip, a footstep or contact schedule, feed-forward torques, scheduled gains.
+//     row [table_cols]   the row of THIS control step, already on chip; row_index: which row of the table that is
+//     table, table_rows, table_cols   the whole table in global memory, for look-ahead (table[i * table_cols + j]); such a read
+//                        is a global load on the reward lane, after the physics: the step's own row is cheaper through `row`
+//   Row of a step: r = (int)step + row0 with `step` as above (the counter BEFORE the step), then
+//     DIAL_TABLE_CLAMP:  row_index = min(max(r, 0), table_rows - 1)      DIAL_TABLE_WRAP:  row_index = ((r % rows) + rows) % rows
+//   so step k of a rollout from a state with counter s0 reads row s0 + k + row0, and the states of a grouped launch or of an
+//   env.step batch each read by their own counter.  The control law of the same control step (user_control.h) sees the SAME row.
+//   The row is valid whenever the reward runs (it does not depend on forward()).  With no table bound: table == row == nullptr,
+//   table_rows == table_cols == 0, row_index == 0.  The table is read-only; its contents are the caller's and may change between
+//   launches (never during one).
 // The function must be deterministic and free of side effects beyond info_user: it runs in every sample of every rollout.
 #pragma once
 #include "../../include/dial_mpc.h"
@@ -46,6 +58,11 @@ struct DialRewardIn {
   const float *qpos, *qvel;                       // post-integration
   const float *xpos, *xquat, *spos, *cdist, *cpos;   // pre-integration forward quantities
   const float *ctrl, *act;                        // the step's control
+  // (appended: reward sources that predate the reference table compile unchanged)
+  const float* row;                               // the step's row of the reference table [table_cols], nullptr without a table
+  int row_index;                                  // which row that is
+  const float* table;                             // the whole table [table_rows][table_cols] in global memory, or nullptr
+  int table_rows, table_cols;
 };
 
 // defined by the plugin's reward source (the plugin's translation unit only; no kernel of libdialhip.so calls it)

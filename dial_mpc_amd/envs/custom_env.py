@@ -9,6 +9,9 @@ A subclass sets
   ``user_params``  names of float fields of its config dataclass; their values, in this order, are the reward's ``params``,
   ``init_keyframe`` the model keyframe env.reset starts from (default "home"),
   ``control_hip``  optional: a control law as HIP source or the path of a ``.hip`` file (the contract of csrc/user_control.h),
+  ``make_table()`` optional: a reference table [rows, cols] of data that changes from step to step (a motion clip, a schedule,
+                   feed-forward torques); every control step hands the reward and the law one row, picked by the state's step
+                   counter -- ``table_row(step, table_row0, rows, table_mode)``.  ``table_mode`` "clamp" (default) or "wrap",
 and registers itself with ``dial_mpc_amd.envs.register_environment`` / ``register_config``.  Without ``control_hip`` control is
 BaseEnv's (act2joint / act2tau with the config's leg_control, kp, kd, action_scale); the sampling range is the joint range of the
 model unless the subclass sets ``self.joint_range``.  Under ``leg_control: torque`` the PD law reads actuator a's joint as
@@ -24,7 +27,7 @@ from __future__ import annotations
 
 import inspect
 import os
-from typing import Any, Dict, List, Sequence
+from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -50,6 +53,18 @@ def torque_joint_convention(model: Dict[str, Any]) -> None:
                          f"indexing of BaseEnv.act2tau); {what}.  Reorder the model's actuators or use leg_control: position")
 
 
+def table_row(step: int, row0: int, rows: int, mode="clamp") -> int:
+    """The reference-table row of the control step whose step counter is `step` (the counter BEFORE the step): the host restatement
+    of the kernels' rule (csrc/user_reward.h).  r = step + row0; "clamp": min(max(r, 0), rows - 1); "wrap": r modulo rows."""
+    from dial_mpc_amd import _lib
+    if rows < 1:
+        raise ValueError(f"table_row: rows = {rows}; a table has at least one row")
+    r = int(step) + int(row0)
+    if _lib.table_mode(mode) == _lib.TABLE_MODES["wrap"]:
+        return r % rows   # (Python's modulo is the non-negative one)
+    return min(max(r, 0), rows - 1)
+
+
 class CustomEnv(BaseEnv):
     task_kind = TASK_USER
     model_path: str = ""
@@ -57,6 +72,8 @@ class CustomEnv(BaseEnv):
     control_hip: str = ""
     user_params: Sequence[str] = ()
     init_keyframe: str = "home"
+    table_mode: str = "clamp"
+    table_row0: int = 0
 
     def __init__(self, config: BaseEnvConfig):
         if not self.model_path or not self.reward_hip:
@@ -130,9 +147,33 @@ class CustomEnv(BaseEnv):
         packed[nq:nq + nv] = np.asarray(_to_numpy(pipeline_state.qvel), dtype=np.float32)
         return self.control(torch.as_tensor(packed, device=ctx.torch_device), np.asarray(_to_numpy(act), dtype=np.float32))[0].cpu().numpy()
 
+    def make_table(self) -> Optional[np.ndarray]:
+        """The env's reference table [rows, cols <= DIAL_USER_TABLE_COLS] (float), or None (default): no table."""
+        return None
+
+    def _table(self) -> Optional[np.ndarray]:
+        """The table contexts of this env bind: what set_table gave last, else make_table(); validated, float32."""
+        from dial_mpc_amd import _lib
+        t = self._table_override if getattr(self, "_table_override", None) is not None else self.make_table()
+        return None if t is None else _lib.user_table_array(t)
+
     def context_kwargs(self) -> Dict[str, Any]:
-        """What a _lib.Context of this env needs beyond (model, task, cfg): its plugin and parameters."""
-        return dict(plugin=self.plugin_path(), user_params=self.user_param_vector())
+        """What a _lib.Context of this env needs beyond (model, task, cfg): its plugin, parameters and reference table."""
+        from dial_mpc_amd import _lib
+        kw = dict(plugin=self.plugin_path(), user_params=self.user_param_vector())
+        table = self._table()
+        if table is not None:
+            kw.update(user_table=table, table_row0=int(self.table_row0), table_mode=_lib.table_mode(self.table_mode))
+        return kw
+
+    def set_table(self, table):
+        """Another reference table (None: back to make_table()): contexts created from now on bind it, and this env's own context
+        rebinds it now.  Returns the bound device tensor of the env's own context (None before the env has one)."""
+        from dial_mpc_amd import _lib
+        self._table_override = None if table is None else _lib.user_table_array(table)
+        if self._ctx is None:
+            return None
+        return self._ctx.set_user_table(self._table(), int(self.table_row0), self.table_mode)
 
     def set_user_params(self, **values) -> None:
         """Change config fields listed in user_params; contexts created from now on, and this env's own, use them."""

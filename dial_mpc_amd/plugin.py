@@ -5,7 +5,8 @@ env.reset kernels (HIP, gfx950).
 compiles that one translation unit with the product flags (``_lib._COMMON + _FAST``) and links a shared library that
 ``libdialhip.so`` loads (``dial_create_plugin``; ``_lib.Context(..., plugin=path)``).  The reward's contract is in
 ``csrc/user_reward.h``.  ``control_src`` adds a control law (contract: ``csrc/user_control.h``) in place of BaseEnv's act2joint /
-PD law; such a plugin carries one more kernel (``user_control_kernel``) and exports a second symbol (``CTRL_SYMBOL``).  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
+PD law; such a plugin carries one more kernel (``user_control_kernel``) and exports a second symbol (``CTRL_SYMBOL``).  Every plugin
+exports ``TABLE_SYMBOL``, the host function behind the reference table (``dial_set_user_table``; no kernel of its own).  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
 hashes every csrc source, ``include/dial_mpc.h``, the reward, the control law (when there is one), the dimensions, the flags and ``hipcc --version``.  hipcc
 cross-compiles, so building needs no GPU.
 """
@@ -27,6 +28,7 @@ from dial_mpc_amd._lib import _COMMON, _CSRC, _FAST, DialHipError
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOL = "dial_plugin_ops_v1"
 CTRL_SYMBOL = "dial_plugin_ctrl_v1"   # exported only by a plugin built with a control law
+TABLE_SYMBOL = "dial_plugin_table_v1"  # exported by every plugin: the reference table's host function (dial_set_user_table)
 DIM_NAMES = ("nq", "nv", "nu", "nbody", "njnt", "ngeom", "nsite", "ncon", "nlim", "nfri")
 _DIM_MACROS = ("NQ", "NV", "NU", "NB", "NJ", "NG", "NS", "NC", "NL", "NFRI")
 

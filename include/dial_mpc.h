@@ -124,6 +124,9 @@ extern "C" {
 #define DIAL_TASK_H1_PUSH_CRATE 6  /* UnitreeH1PushCrateEnv.step (unitree_h1_env.py:418-566) */
 #define DIAL_TASK_USER 7       /* a user reward compiled into a task plugin (dial_create_plugin, csrc/user_reward.h) */
 #define DIAL_USER_PARAMS 32    /* float task parameters of a user reward (dial_set_user_params)                       */
+#define DIAL_USER_TABLE_COLS 64 /* most columns of a task plugin's reference table (dial_set_user_table)               */
+#define DIAL_TABLE_CLAMP 0     /* reference-table row of a step: min(max(step + row0, 0), rows - 1)                    */
+#define DIAL_TABLE_WRAP  1     /* ... or (step + row0) modulo rows, non-negative                                       */
 
 /* packed-state info slots (floats; integers are stored as exactly representable floats) */
 #define DIAL_INFO_STEP 0
@@ -567,6 +570,21 @@ int dial_set_plan_params(dial_ctx* ctx, const float* params, int rows);
  * Nothing is stepped and no state is written.  Fails with DIAL_ERR_ARG and a message when n < 1, when n exceeds the bound
  * per-plan rows, or when the context has no control law (no task plugin, or a plugin built without one). */
 int dial_user_control(dial_ctx* ctx, const float* states, const float* actions, int n, float* ctrl_out, void* stream);
+/* The reference table of a task-plugin context: data that changes from step to step (a motion clip, a footstep or contact
+ * schedule, feed-forward torques, scheduled gains).  table: [rows, cols] contiguous float32 DEVICE memory, caller-owned and BOUND,
+ * not copied (like dial_set_plan_params): the caller keeps it alive while bound and may rewrite its contents on the launching
+ * stream between launches without a new call.  Every control step hands ONE row to the user reward and the user control law
+ * (csrc/user_reward.h, csrc/user_control.h: row, row_index, table, table_rows, table_cols), picked by the state's own step
+ * counter: r = (int)step + row0, then DIAL_TABLE_CLAMP: min(max(r, 0), rows - 1), DIAL_TABLE_WRAP: ((r % rows) + rows) % rows.
+ * Step k of a rollout from a state with counter s0 reads row s0 + k + row0; the plans of a grouped launch and the states of
+ * dial_env_step_batch / dial_user_control each read by their own state's counter (counters are exact up to 2^24; under
+ * DIAL_TABLE_CLAMP a row0 beyond +-2^30 acts as +-2^30).  One table per context; table == NULL with rows == 0 unbinds (the
+ * reward and the law then see null pointers and zero sizes).
+ * Synchronises the device and re-uploads the constants, like dial_set_user_params: not for use inside a stream capture.
+ * Fails with DIAL_ERR_ARG and a message that starts with "dial_set_user_table: " on a null context, a context without a task
+ * plugin, rows < 1 or rows > 1 << 24 with a non-NULL table, cols outside 1 .. DIAL_USER_TABLE_COLS, a NULL table with rows != 0,
+ * or an unknown mode; with DIAL_ERR_UNSUPPORTED when the plugin does not export dial_plugin_table_v1 (built from older sources). */
+int dial_set_user_table(dial_ctx* ctx, const float* table, int rows, int cols, int row0, int mode);
 
 /* Plant simulator (deploy/dial_sim.py): M plants advanced by K physics steps in ONE launch, each step applying one row of the plan
  * the planner published -- what the reference's dial_sim.py does with MuJoCo's mj_step at sim_dt.  The context is an ordinary
