@@ -246,6 +246,7 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
 
 # dial_plant_step flags (include/dial_mpc.h)
 PLANT_CTRL, PLANT_PD, PLANT_HOLD_FIRST = (_abi.MACROS[k] for k in ("DIAL_PLANT_CTRL", "DIAL_PLANT_PD", "DIAL_PLANT_HOLD_FIRST"))
+PLANT_LAW = _abi.MACROS["DIAL_PLANT_LAW"]   # a task plugin built with a plant and a control law: the rows are normalised actions
 
 
 def plan_param_rows(rows) -> np.ndarray:
@@ -501,7 +502,8 @@ class Context:
     def plant_step(self, states, t, plan_time, ctrl, ctrl_dt: float, sim_dt: float, K: int, flags: int, trace=None):
         """K physics steps of M plants in one launch, all in place: states [M, state_size] float32, t [M] float64 clocks,
         plan_time [M] float32, ctrl [M, T, nu] float32 (the published rows), trace [M, K, 1 + nq + nv + nu] float32 or None.
-        The context's model must have timestep = sim_dt (Plant / env.make_plant build one)."""
+        The context's model must have timestep = sim_dt (Plant / env.make_plant build one).  A task-plugin context needs a plugin
+        built with a plant (build_plugin(plant=True)); PLANT_LAW, its law at every sim step, needs one with a control law too."""
         import torch
         M = int(states.shape[0])
         assert states.dim() == 2 and states.shape[1] == self.state_size, "states: [M, state_size]"

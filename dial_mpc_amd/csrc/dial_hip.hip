@@ -23,6 +23,7 @@
 
 #include "kernel_list.h"
 #include "plant_kernel.h"
+#include "plant_plugin.h"
 #include "plugin_ops.h"
 
 // the kernels are compiled in their own translation units, one per robot family (kern_family.hip, built in parallel)
@@ -350,6 +351,7 @@ struct dial_ctx {
   const dial_plugin_ops* plug = nullptr;   // inst 7: the plugin's host functions (the library stays loaded for the process)
   const dial_plugin_ctrl* plug_ctrl = nullptr;   // inst 7: the plugin's user control law (dial_user_control), nullptr when it has none
   const dial_plugin_table* plug_table = nullptr; // inst 7: the plugin's reference-table function (dial_set_user_table), nullptr: an older plugin
+  const dial_plugin_plant* plug_plant = nullptr; // inst 7: the plugin's plant kernel (dial_plant_step), nullptr: built without one
   std::vector<char> plug_cm;               // inst 7: host copy of the constants (dial_set_user_params rewrites the parameters)
   const float* plan_params = nullptr;      // inst 7: per-plan task parameters (dial_set_plan_params), caller-owned device rows ...
   int plan_rows = 0;                       // ... [plan_rows, DIAL_USER_PARAMS]; nullptr: every launch reads the shared ones
@@ -515,8 +517,20 @@ int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task*
     if (tab->cmodel_bytes != ops->cmodel_bytes || tab->sizeof_reward_in != sizeof(DialRewardIn) || tab->sizeof_control_in != sizeof(DialControlIn))
       return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's reference-table entry was built against another version of the library (ABI mismatch; rebuild it)");
   }
+  // the plant kernel's table: a fourth symbol, exported only by a plugin built with a plant (build_plugin(plant=True))
+  const dial_plugin_plant* pla = nullptr;
+  if (dial_plugin_plant_entry pentry = (dial_plugin_plant_entry)dlsym(h, DIAL_PLUGIN_PLANT_SYMBOL)) {
+    pla = pentry();
+    if (!pla) return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + plugin_path + ": " DIAL_PLUGIN_PLANT_SYMBOL " returned no table");
+    if (pla->version != DIAL_PLUGIN_PLANT_VERSION)
+      return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: stale plugin: its plant table reports version ") + std::to_string(pla->version) +
+                                         ", the library needs version " + std::to_string(DIAL_PLUGIN_PLANT_VERSION) + " (rebuild it from the current sources)");
+    if (pla->cmodel_bytes != ops->cmodel_bytes || pla->sizeof_control_in != sizeof(DialControlIn) || pla->nq != model->nq || pla->nv != model->nv ||
+        pla->nu != model->nu || (pla->has_law != 0) != (ctl != nullptr) || !pla->launch)
+      return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's plant table was built against another version of the library (ABI mismatch; rebuild it)");
+  }
   const int rc = create_impl(out, model, task, cfg, device, -1, opts, ops, params, n_params);
-  if (rc == DIAL_OK) { (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; }
+  if (rc == DIAL_OK) { (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; (*out)->plug_plant = pla; }
   return rc;
 }
 
@@ -1590,9 +1604,19 @@ int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_t
   if (!states || !t || !plan_time || !ctrl) return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: null argument (states, t, plan_time and ctrl are required)");
   if (K < 1 || T < 1 || M < 1) return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: K, T and M must be >= 1");
   if (M > DIAL_MAX_PLANTS) return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: M exceeds DIAL_MAX_PLANTS");
-  const int mode = flags & (DIAL_PLANT_CTRL | DIAL_PLANT_PD);
-  if ((flags & ~(DIAL_PLANT_CTRL | DIAL_PLANT_PD | DIAL_PLANT_HOLD_FIRST)) != 0 || (mode != DIAL_PLANT_CTRL && mode != DIAL_PLANT_PD))
-    return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: flags must hold exactly one of DIAL_PLANT_CTRL / DIAL_PLANT_PD, optionally DIAL_PLANT_HOLD_FIRST");
+  const int mode = flags & (DIAL_PLANT_CTRL | DIAL_PLANT_PD | DIAL_PLANT_LAW);
+  if ((flags & ~(DIAL_PLANT_CTRL | DIAL_PLANT_PD | DIAL_PLANT_LAW | DIAL_PLANT_HOLD_FIRST)) != 0 ||
+      (mode != DIAL_PLANT_CTRL && mode != DIAL_PLANT_PD && mode != DIAL_PLANT_LAW))
+    return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: flags must hold exactly one of DIAL_PLANT_CTRL / DIAL_PLANT_PD / DIAL_PLANT_LAW, optionally "
+                                   "DIAL_PLANT_HOLD_FIRST");
+  if (mode == DIAL_PLANT_LAW) {
+    if (!ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: DIAL_PLANT_LAW on a context without a task plugin (the law is a task plugin's: dial_create_plugin)");
+    if (!ctx->plug_ctrl)
+      return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: DIAL_PLANT_LAW, but the context's task plugin was built without a user control law (build_plugin(control_src=))");
+    if (ctx->plan_params)
+      return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: DIAL_PLANT_LAW while per-plan task parameters are bound (the plant's law reads the shared parameters; "
+                                     "unbind them with dial_set_plan_params(NULL))");
+  }
   if (mode == DIAL_PLANT_PD)
     for (int a = 0; a < ctx->hm.nu; a++)
       if (ctx->hm.act_isposition[a])
@@ -1600,11 +1624,27 @@ int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_t
   if (!(ctrl_dt > 0.0) || !(sim_dt > 0.0)) return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: ctrl_dt and sim_dt must be > 0");
   if ((float)sim_dt != ctx->hm.timestep)
     return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: sim_dt differs from the model's timestep (create the context with timestep = sim_dt)");
-  if (ctx->plug) return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: task-plugin contexts have no plant (custom environments are not simulated)");
+  if (ctx->plug && !ctx->plug_plant)
+    return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: task-plugin contexts have no plant unless the plugin was built with one (build_plugin(plant=True); "
+                                           "CustomEnv.make_plant does)");
+  if (ctx->plug && mode == DIAL_PLANT_PD) {   // the PD law's joint indexing (envs/custom_env.py: torque_joint_convention)
+    const dial_model& hm = ctx->hm;
+    bool fits = hm.njnt > 0 && hm.jnt_type[0] == DIAL_JNT_FREE && hm.jnt_qposadr[0] == 0;
+    for (int a = 0; a < hm.nu && fits; a++) fits = hm.act_qposadr[a] == 7 + a && hm.act_dofadr[a] == 6 + a;
+    if (!fits)
+      return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: DIAL_PLANT_PD needs actuator a to drive qpos[7 + a] / dof 6 + a after a free base joint (the PD law's "
+                                     "joint indexing); this model differs");
+  }
 #ifdef DIAL_IEEE_BUILD
   (void)trace; (void)stream;
   return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: the IEEE measurement build carries no plant (use the product library)");
 #else
+  if (ctx->plug) {   // the plugin's own plant kernel, at the env.step workspace of the context
+    if (int rc = check_sticky(ctx)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, ctx->plug_plant->launch(ctx->dcm, ctx->lds_bytes, (hipStream_t)stream, states, t, plan_time, ctrl, T, ctrl_dt, sim_dt, K, flags, trace, M));
+    return DIAL_OK;
+  }
   const dial_plant_ops* ops = plant_lib().ops;
   if (!ops) return fail(ctx, DIAL_ERR_UNSUPPORTED, plant_lib().err);
   if (ctx->inst < 0 || ctx->inst >= DIAL_PLANT_INSTS || ops->cmodel_bytes[ctx->inst] != cmodel_bytes_of(ctx->inst))

@@ -7,7 +7,15 @@
 //   dial_user_control.hip the user's definition of dial_user_control (user_control.h states the contract)
 // Such a plugin carries one more kernel, user_control_kernel, and exports a second table (plugin_ops.h: dial_plugin_ctrl).
 // Every plugin exports a third, dial_plugin_table (the reference table of dial_set_user_table: host code only, no kernel).
+// A plugin built with a plant (-DDIAL_PLUGIN_PLANT=1) carries plant_user_kernel and exports a fourth, dial_plugin_plant
+// (plant_plugin.h: dial_plant_step on the plugin's contexts).
 #include "plugin_ops.h"
+#ifndef DIAL_PLUGIN_PLANT
+#define DIAL_PLUGIN_PLANT 0
+#endif
+#if DIAL_PLUGIN_PLANT
+#include "plant_plugin.h"
+#endif
 #include "dial_plugin_dims.h"
 #include "dial_user_reward.hip"
 #ifndef DIAL_PLUGIN_USER_CTRL
@@ -49,5 +57,14 @@ template __global__ void user_control_kernel<DimsPlugin>(const CModel<DimsPlugin
 
 extern "C" __attribute__((visibility("default"))) const dial_plugin_ctrl* dial_plugin_ctrl_v1(void) {
   return PluginCtrl<DimsPlugin>::table();
+}
+#endif
+
+#if DIAL_PLUGIN_PLANT
+template __global__ void plant_user_kernel<DimsPlugin>(const CModel<DimsPlugin>*, float*, double*, const float*, const float*, int, double, double,
+                                                        int, int, float*);
+
+extern "C" __attribute__((visibility("default"))) const dial_plugin_plant* dial_plugin_plant_v1(void) {
+  return PluginPlant<DimsPlugin>::table();
 }
 #endif

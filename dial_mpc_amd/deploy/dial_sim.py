@@ -48,6 +48,10 @@ class DialSim:
         self.n_acts = dial_config.Hsample + 1
         self.sync_mode = sim_config.sync_mode
         self.leg_control = sim_config.sim_leg_control
+        if self.leg_control == "law":
+            raise ValueError("[dial-mpc-sim] sim_leg_control: law is not supported here: the six shared-memory segments carry joint targets "
+                             "(acts_shm) and actuator values (tau_shm), no normalised actions.  Use sim_leg_control: torque -- the planner "
+                             "publishes the env's control law as tau_shm -- or step a deploy.plant.Plant(env, sim_dt, 'law') in process")
         if sim_config.plot:
             print("[dial-mpc-sim] plot: true is not supported (no viewer / plots on this path); continuing without")
         scene = get_model_path(sim_config.robot_name, sim_config.scene_name)

@@ -36,28 +36,52 @@ def sync_steps(t: float, plan_time, ctrl_dt: float, sim_dt: float) -> int:
     return n
 
 
+def law_step(t: float, ctrl_dt: float) -> int:
+    """The control step the clock t is in, as DIAL_PLANT_LAW hands it to a custom env's control law (csrc/plant_plugin.h:
+    plant_law_step): the fp64 quotient t / ctrl_dt truncated toward zero, 0 when the quotient is not >= 0 (negative clocks, NaN),
+    at most 2^24."""
+    q = float(t) / float(ctrl_dt)
+    if not q >= 0.0:
+        return 0
+    if q >= 16777216.0:
+        return 1 << 24
+    return int(q)
+
+
 class Plant:
     """M copies of an env's plant, stepped on the GPU.  ``leg_control``: "torque" -- the rows are the actuators' ctrl as they are
     (DIAL_PLANT_CTRL, dial_sim.py's ``data.ctrl = tau_shared[k]``); "position" -- the rows are joint targets, turned into torques by
     the env's PD law at every sim step (DIAL_PLANT_PD), or, on models whose actuators are position actuators (the Allegro), handed to
-    them as their ctrl (DIAL_PLANT_CTRL)."""
+    them as their ctrl (DIAL_PLANT_CTRL).  A custom environment (envs/custom_env.py) is stepped by the plant kernel of its own task
+    plugin (csrc/plant_plugin.h); "position" there needs the PD law's joint indexing (torque_joint_convention), and an env with a
+    control law (control_hip) has a third mode, "law": the rows are normalised actions and the law runs at every sim step from the
+    plant's current state (DIAL_PLANT_LAW; law_step is the step counter it sees)."""
 
     def __init__(self, env, sim_dt: float, leg_control: str = "torque", M: int = 1, device: Optional[int] = None):
         import torch
         from dial_mpc_amd import _lib
-        if leg_control not in ("torque", "position"):
-            raise ValueError(f"sim_leg_control must be 'torque' or 'position', not {leg_control!r}")
+        from dial_mpc_amd.envs.custom_env import CustomEnv, torque_joint_convention
+        custom = isinstance(env, CustomEnv)
+        if leg_control not in ("torque", "position", "law"):
+            raise ValueError(f"sim_leg_control must be 'torque', 'position' or 'law', not {leg_control!r}")
+        if leg_control == "law" and not (custom and env.control_hip):
+            raise ValueError(f"sim_leg_control: law needs a custom environment with a control law (control_hip); {type(env).__name__} has none")
+        nu = int(env.sys.nu)
+        positional = bool(np.any(np.asarray(env.make_model().act_isposition)[:nu]))
+        if leg_control == "law":
+            self.flags = _lib.PLANT_LAW
+        elif leg_control == "torque" or positional:
+            self.flags = _lib.PLANT_CTRL
+        else:
+            if custom:
+                torque_joint_convention(env.sys.model)
+            self.flags = _lib.PLANT_PD
         self.env, self.sim_dt, self.M = env, float(sim_dt), int(M)
         self.ctrl_dt = float(env._config.dt)
         self._hold = _lib.PLANT_HOLD_FIRST
         self.ctx = env.make_plant(self.sim_dt, device=device)
         self.nq, self.nv, self.nu = self.ctx.nq, self.ctx.nv, self.ctx.nu
         self.width = 1 + self.nq + self.nv + self.nu          # trace / record row: [t, qpos, qvel, ctrl]
-        positional = bool(np.any(np.asarray(env.make_model().act_isposition)[: self.nu]))
-        if leg_control == "torque" or positional:
-            self.flags = _lib.PLANT_CTRL
-        else:
-            self.flags = _lib.PLANT_PD
         self.dev = self.ctx.torch_device
         self._torch = torch
         self.reset()

@@ -6,7 +6,9 @@ compiles that one translation unit with the product flags (``_lib._COMMON + _FAS
 ``libdialhip.so`` loads (``dial_create_plugin``; ``_lib.Context(..., plugin=path)``).  The reward's contract is in
 ``csrc/user_reward.h``.  ``control_src`` adds a control law (contract: ``csrc/user_control.h``) in place of BaseEnv's act2joint /
 PD law; such a plugin carries one more kernel (``user_control_kernel``) and exports a second symbol (``CTRL_SYMBOL``).  Every plugin
-exports ``TABLE_SYMBOL``, the host function behind the reference table (``dial_set_user_table``; no kernel of its own).  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
+exports ``TABLE_SYMBOL``, the host function behind the reference table (``dial_set_user_table``; no kernel of its own).
+``plant=True`` adds the plant simulator's kernel at the model's dimensions (``csrc/plant_plugin.h``: ``plant_user_kernel``,
+``dial_plant_step`` on the plugin's contexts) and a fourth symbol (``PLANT_SYMBOL``); a plugin built without it is unchanged.  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
 hashes every csrc source, ``include/dial_mpc.h``, the reward, the control law (when there is one), the dimensions, the flags and ``hipcc --version``.  hipcc
 cross-compiles, so building needs no GPU.
 """
@@ -29,6 +31,7 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOL = "dial_plugin_ops_v1"
 CTRL_SYMBOL = "dial_plugin_ctrl_v1"   # exported only by a plugin built with a control law
 TABLE_SYMBOL = "dial_plugin_table_v1"  # exported by every plugin: the reference table's host function (dial_set_user_table)
+PLANT_SYMBOL = "dial_plugin_plant_v1"  # exported only by a plugin built with plant=True: the plant kernel's table (dial_plant_step)
 DIM_NAMES = ("nq", "nv", "nu", "nbody", "njnt", "ngeom", "nsite", "ncon", "nlim", "nfri")
 _DIM_MACROS = ("NQ", "NV", "NU", "NB", "NJ", "NG", "NS", "NC", "NL", "NFRI")
 
@@ -112,13 +115,17 @@ def plugin_key(model, reward_src: str, flags: Sequence[str], control_src: Option
 
 
 def build_plugin(model, reward_src: str, flags: Optional[Sequence[str]] = None, verbose: bool = False,
-                 control_src: Optional[str] = None) -> str:
+                 control_src: Optional[str] = None, plant: bool = False) -> str:
     """Compile (or find in the cache) the task plugin of `model` with the reward `reward_src` (HIP source text, or the path of a
-    .hip file) and, optionally, the control law `control_src` (the same two forms) -> path of the shared library.  A compile error
-    in either raises DialHipError with hipcc's own message."""
+    .hip file) and, optionally, the control law `control_src` (the same two forms) -> path of the shared library.  plant=True:
+    the plugin also carries the plant simulator's kernel (-DDIAL_PLUGIN_PLANT=1; the define is one of the flags the cache key
+    hashes, so it is another library than the plugin without it).  A compile error in either source raises DialHipError with
+    hipcc's own message."""
     import fcntl
     check_model(model)
     flags = list(_COMMON + _FAST if flags is None else flags)
+    if plant:
+        flags.append("-DDIAL_PLUGIN_PLANT=1")
     reward = _read_reward(reward_src)
     control = None if control_src is None else _read_reward(control_src)
     key = plugin_key(model, reward, flags, control)[:24]

@@ -64,10 +64,11 @@ extern "C" {
 #define DIAL_MAX_PLANS 1024 /* dial_options.plan_cap: plans of one grouped launch (dial_reverse_once_batch)    */
 #define DIAL_MAX_PLANTS 65536 /* dial_plant_step: plants of one launch                                          */
 
-/* dial_plant_step flags: exactly one of CTRL / PD, optionally HOLD_FIRST */
+/* dial_plant_step flags: exactly one of CTRL / PD / LAW, optionally HOLD_FIRST */
 #define DIAL_PLANT_CTRL 1        /* the control row is the actuators' ctrl as it is (MuJoCo's data.ctrl = row)          */
 #define DIAL_PLANT_PD 2          /* the control row is a joint target: ctrl = clip(kp (q* - q) - kd qd, tau_range) per step */
 #define DIAL_PLANT_HOLD_FIRST 4  /* every step applies row 0 (sync mode); otherwise the row follows the clock               */
+#define DIAL_PLANT_LAW 8         /* the control row is a normalised action: ctrl = the task plugin's user control law per step */
 
 /* joint types (MuJoCo numbering) */
 #define DIAL_JNT_FREE 0
@@ -598,11 +599,20 @@ int dial_set_user_table(dial_ctx* ctx, const float* table, int rows, int cols, i
  * DIAL_PLANT_CTRL: ctrl = row, applied by the model's actuators (ctrlrange clip where limited, motor or position actuators).
  * DIAL_PLANT_PD: ctrl = clip(kp (row - q) - kd qd, tau_range) at every step, kp / kd / tau_range of the task (act2tau without
  * act2joint); refused on models with position actuators.
+ * Task-plugin contexts (dial_create_plugin) are served by the plugin's own plant kernel when the plugin was built with one
+ * (build_plugin(plant=True): the optional table dial_plugin_plant_v1, csrc/plant_plugin.h), with the same arguments and rules;
+ * DIAL_PLANT_PD there needs actuator a on qpos[7 + a] / dof 6 + a after a free base joint.  Such a plugin with a user control law
+ * adds DIAL_PLANT_LAW: the row is a normalised action in [-1, 1] and the law (csrc/user_control.h) runs at EVERY sim step from the
+ * plant's current qpos / qvel; its value is the step's ctrl (and the trace's), applied by the actuators like any ctrl.  The law
+ * sees step = the control step the clock is in -- trunc(t / ctrl_dt) in fp64, 0 when that quotient is not >= 0, at most 2^24 --,
+ * dt = (float)ctrl_dt, act = the picked row, info_user = the state's slots as they are, the shared task parameters, and the
+ * reference-table row of that step.  DIAL_PLANT_LAW fails with DIAL_ERR_ARG combined with another mode, on a context without a
+ * task plugin, on a plugin without a law, and while per-plan task parameters are bound (dial_set_plan_params).
  *   trace:[M,K,1+nq+nv+nu] or NULL: per step, BEFORE it, [(float)t, qpos, qvel, ctrl applied] (dial_sim.py's record row).
  * Every pointer is device memory.  The kernels live in libdialplant.so next to this library (loaded on first use).
  * Fails with DIAL_ERR_ARG and a message on null pointers, K / T / M < 1, M > DIAL_MAX_PLANTS, unknown flags, DIAL_PLANT_PD on a
- * model with position actuators, or (float)sim_dt != the model's timestep; with DIAL_ERR_UNSUPPORTED on task-plugin contexts, when
- * libdialplant.so is missing, and in the IEEE measurement build. */
+ * model with position actuators, or (float)sim_dt != the model's timestep; with DIAL_ERR_UNSUPPORTED on contexts of a task plugin
+ * built without a plant, when libdialplant.so is missing, and in the IEEE measurement build. */
 int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_time, const float* ctrl, int T, double ctrl_dt,
                     double sim_dt, int K, int flags, float* trace, int M, void* stream);
 
