@@ -356,6 +356,7 @@ struct dial_ctx {
   const float* plan_params = nullptr;      // inst 7: per-plan task parameters (dial_set_plan_params), caller-owned device rows ...
   int plan_rows = 0;                       // ... [plan_rows, DIAL_USER_PARAMS]; nullptr: every launch reads the shared ones
   void* dcm = nullptr;        // CModel<D> of the chosen instantiation (device)
+  size_t dcm_bytes = 0;       // sizeof(CModel<D>) as uploaded (dial_plant_step checks libdialplant.so's constants against it)
   dial_task* dtask = nullptr;
   dial_cfg* dcfg = nullptr;
   int con_cap = 0, ovf_words = 0;   // generic instantiation: contact cap of the rollout kernel's LDS workspace, words of one overflow area
@@ -423,6 +424,23 @@ static int fail(dial_ctx* ctx, int code, const std::string& msg) {
     if (e_ != hipSuccess)                                                                      \
       return fail(ctx, DIAL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
   } while (0)
+
+// dial_create_plugin: an OPTIONAL table of a task plugin (dial_plugin_ctrl / dial_plugin_table / dial_plugin_plant; `what` is its name in the messages):
+// *tab stays nullptr when the plugin does not export `symbol`; a symbol that returns no table, or a table of another version, is an
+// error.  The sizes and dimensions each table records are the caller's to compare.
+template <class Tab>
+static int plugin_table(void* h, const char* plugin_path, const char* symbol, const char* what, int version, const Tab** tab) {
+  typedef const Tab* (*entry_fn)(void);
+  *tab = nullptr;
+  entry_fn entry = (entry_fn)dlsym(h, symbol);
+  if (!entry) return DIAL_OK;
+  *tab = entry();
+  if (!*tab) return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + plugin_path + ": " + symbol + " returned no table");
+  if ((*tab)->version != version)
+    return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: stale plugin: its ") + what + " reports version " + std::to_string((*tab)->version) +
+                                       ", the library needs version " + std::to_string(version) + " (rebuild it from the current sources)");
+  return DIAL_OK;
+}
 
 extern "C" {
 
@@ -495,40 +513,22 @@ int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task*
   for (int k = 0; k < 10; k++)
     if (md[k] != ops->dims[k]) return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the model's dimensions differ from the plugin's (rebuild the plugin for this model)");
   // the user control law's table: a second symbol, absent from a plugin built without a law
-  const dial_plugin_ctrl* ctl = nullptr;
-  if (dial_plugin_ctrl_entry centry = (dial_plugin_ctrl_entry)dlsym(h, DIAL_PLUGIN_CTRL_SYMBOL)) {
-    ctl = centry();
-    if (!ctl) return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + plugin_path + ": " DIAL_PLUGIN_CTRL_SYMBOL " returned no table");
-    if (ctl->version != DIAL_PLUGIN_CTRL_VERSION)
-      return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: stale plugin: its control-law table reports version ") + std::to_string(ctl->version) +
-                                         ", the library needs version " + std::to_string(DIAL_PLUGIN_CTRL_VERSION) + " (rebuild it from the current sources)");
-    if (ctl->cmodel_bytes != ops->cmodel_bytes || ctl->sizeof_control_in != sizeof(DialControlIn) || ctl->nq != model->nq || ctl->nv != model->nv ||
-        ctl->nu != model->nu)
-      return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's control-law table was built against another version of the library (ABI mismatch; rebuild it)");
-  }
+  const dial_plugin_ctrl* ctl;
+  if (int rc = plugin_table(h, plugin_path, DIAL_PLUGIN_CTRL_SYMBOL, "control-law table", DIAL_PLUGIN_CTRL_VERSION, &ctl)) return rc;
+  if (ctl && (ctl->cmodel_bytes != ops->cmodel_bytes || ctl->sizeof_control_in != sizeof(DialControlIn) || ctl->nq != model->nq || ctl->nv != model->nv ||
+              ctl->nu != model->nu))
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's control-law table was built against another version of the library (ABI mismatch; rebuild it)");
   // the reference table's function: a third symbol, absent from a plugin built before the table existed
-  const dial_plugin_table* tab = nullptr;
-  if (dial_plugin_table_entry tentry = (dial_plugin_table_entry)dlsym(h, DIAL_PLUGIN_TABLE_SYMBOL)) {
-    tab = tentry();
-    if (!tab) return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + plugin_path + ": " DIAL_PLUGIN_TABLE_SYMBOL " returned no table");
-    if (tab->version != DIAL_PLUGIN_TABLE_VERSION)
-      return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: stale plugin: its reference-table entry reports version ") + std::to_string(tab->version) +
-                                         ", the library needs version " + std::to_string(DIAL_PLUGIN_TABLE_VERSION) + " (rebuild it from the current sources)");
-    if (tab->cmodel_bytes != ops->cmodel_bytes || tab->sizeof_reward_in != sizeof(DialRewardIn) || tab->sizeof_control_in != sizeof(DialControlIn))
-      return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's reference-table entry was built against another version of the library (ABI mismatch; rebuild it)");
-  }
+  const dial_plugin_table* tab;
+  if (int rc = plugin_table(h, plugin_path, DIAL_PLUGIN_TABLE_SYMBOL, "reference-table entry", DIAL_PLUGIN_TABLE_VERSION, &tab)) return rc;
+  if (tab && (tab->cmodel_bytes != ops->cmodel_bytes || tab->sizeof_reward_in != sizeof(DialRewardIn) || tab->sizeof_control_in != sizeof(DialControlIn)))
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's reference-table entry was built against another version of the library (ABI mismatch; rebuild it)");
   // the plant kernel's table: a fourth symbol, exported only by a plugin built with a plant (build_plugin(plant=True))
-  const dial_plugin_plant* pla = nullptr;
-  if (dial_plugin_plant_entry pentry = (dial_plugin_plant_entry)dlsym(h, DIAL_PLUGIN_PLANT_SYMBOL)) {
-    pla = pentry();
-    if (!pla) return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + plugin_path + ": " DIAL_PLUGIN_PLANT_SYMBOL " returned no table");
-    if (pla->version != DIAL_PLUGIN_PLANT_VERSION)
-      return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: stale plugin: its plant table reports version ") + std::to_string(pla->version) +
-                                         ", the library needs version " + std::to_string(DIAL_PLUGIN_PLANT_VERSION) + " (rebuild it from the current sources)");
-    if (pla->cmodel_bytes != ops->cmodel_bytes || pla->sizeof_control_in != sizeof(DialControlIn) || pla->nq != model->nq || pla->nv != model->nv ||
-        pla->nu != model->nu || (pla->has_law != 0) != (ctl != nullptr) || !pla->launch)
-      return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's plant table was built against another version of the library (ABI mismatch; rebuild it)");
-  }
+  const dial_plugin_plant* pla;
+  if (int rc = plugin_table(h, plugin_path, DIAL_PLUGIN_PLANT_SYMBOL, "plant table", DIAL_PLUGIN_PLANT_VERSION, &pla)) return rc;
+  if (pla && (pla->cmodel_bytes != ops->cmodel_bytes || pla->sizeof_control_in != sizeof(DialControlIn) || pla->nq != model->nq || pla->nv != model->nv ||
+              pla->nu != model->nu || (pla->has_law != 0) != (ctl != nullptr) || !pla->launch))
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's plant table was built against another version of the library (ABI mismatch; rebuild it)");
   const int rc = create_impl(out, model, task, cfg, device, -1, opts, ops, params, n_params);
   if (rc == DIAL_OK) { (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; (*out)->plug_plant = pla; }
   return rc;
@@ -744,6 +744,7 @@ static int create_impl(dial_ctx** out, const dial_model* model, const dial_task*
 #ifdef DIAL_PROFILE
       ctx->lds_rollout += 16 + (size_t)ctx->wpb * 32 * sizeof(unsigned long long);
 #endif
+      ctx->dcm_bytes = sizeof(CModel<D>);
       hipError_t e = hipMalloc(&ctx->dcm, (sizeof(CModel<D>) + 15) / 16 * 16);   // (the kernels stage it with 16-byte copies)
       if (e == hipSuccess) e = hipMemcpy(ctx->dcm, h, sizeof(CModel<D>), hipMemcpyHostToDevice);
       delete h;
@@ -769,6 +770,7 @@ static int create_impl(dial_ctx** out, const dial_model* model, const dial_task*
       ctx->lds_rollout = ctx->cm_bytes + (size_t)ctx->wpb * ctx->ws_words * sizeof(float);
       ctx->plug_cm.assign(plug->cmodel_bytes, 0);
       plug->fill(ctx->plug_cm.data(), model, task, &ctx->hd, params, n_params);
+      ctx->dcm_bytes = plug->cmodel_bytes;
       hipError_t e = hipMalloc(&ctx->dcm, (plug->cmodel_bytes + 15) / 16 * 16);
       if (e == hipSuccess) e = hipMemcpy(ctx->dcm, ctx->plug_cm.data(), plug->cmodel_bytes, hipMemcpyHostToDevice);
       urc = e == hipSuccess ? DIAL_OK : DIAL_ERR_HIP;
@@ -1584,18 +1586,6 @@ static const PlantLib& plant_lib() {
   static const PlantLib lib = plant_load();   // (once per process, thread-safe initialisation)
   return lib;
 }
-
-static size_t cmodel_bytes_of(int inst) {
-  switch (inst) {
-    case 1: return sizeof(CModel<DimsGo2>);
-    case 2: return sizeof(CModel<DimsH1>);
-    case 3: return sizeof(CModel<DimsH1Loco>);
-    case 4: return sizeof(CModel<DimsAllegro>);
-    case 5: return sizeof(CModel<DimsGo2Crate>);
-    case 6: return sizeof(CModel<DimsH1PushCrate>);
-    default: return sizeof(CModel<DimsMax>);
-  }
-}
 #endif
 
 int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_time, const float* ctrl, int T, double ctrl_dt,
@@ -1639,20 +1629,18 @@ int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_t
   (void)trace; (void)stream;
   return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: the IEEE measurement build carries no plant (use the product library)");
 #else
-  if (ctx->plug) {   // the plugin's own plant kernel, at the env.step workspace of the context
-    if (int rc = check_sticky(ctx)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, ctx->plug_plant->launch(ctx->dcm, ctx->lds_bytes, (hipStream_t)stream, states, t, plan_time, ctrl, T, ctrl_dt, sim_dt, K, flags, trace, M));
-    return DIAL_OK;
+  dial_plant_launch_fn launch = nullptr;
+  if (ctx->plug) launch = ctx->plug_plant->launch;   // the plugin's own plant kernel, at the env.step workspace of the context
+  else {
+    const dial_plant_ops* ops = plant_lib().ops;
+    if (!ops) return fail(ctx, DIAL_ERR_UNSUPPORTED, plant_lib().err);
+    if (ctx->inst < 0 || ctx->inst >= DIAL_PLANT_INSTS || ops->cmodel_bytes[ctx->inst] != ctx->dcm_bytes)
+      return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: libdialplant.so does not match this library's constants (rebuild both)");
+    launch = ops->launch[ctx->inst];
   }
-  const dial_plant_ops* ops = plant_lib().ops;
-  if (!ops) return fail(ctx, DIAL_ERR_UNSUPPORTED, plant_lib().err);
-  if (ctx->inst < 0 || ctx->inst >= DIAL_PLANT_INSTS || ops->cmodel_bytes[ctx->inst] != cmodel_bytes_of(ctx->inst))
-    return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: libdialplant.so does not match this library's constants (rebuild both)");
   if (int rc = check_sticky(ctx)) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, ops->launch[ctx->inst](ctx->dcm, ctx->lds_bytes, (hipStream_t)stream, states, t, plan_time, ctrl, T, ctrl_dt, sim_dt, K, flags,
-                                      trace, M));
+  HIP_TRY(ctx, launch(ctx->dcm, ctx->lds_bytes, (hipStream_t)stream, states, t, plan_time, ctrl, T, ctrl_dt, sim_dt, K, flags, trace, M));
   return DIAL_OK;
 #endif
 }

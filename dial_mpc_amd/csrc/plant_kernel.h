@@ -2,8 +2,20 @@
 // workgroup) each, K physics steps per launch.  Each step applies one row of the plan the planner published and runs the env.step's
 // own physics -- forward + euler through the generic control path (no control tables, no reward, no act2joint, no gait clock;
 // the info words are left untouched).  The constants are staged once, the state (qpos, qvel, qacc_warmstart) stays resident in
-// LDS across the K steps.  Compiled into libdialplant.so (plant_family.hip, one translation unit per robot family), never into
-// libdialhip.so, whose code objects stay as shipped; libdialhip.so reaches these launches through the table below (dlopen).
+// LDS across the K steps; the clock is fp64, the row follows dial_sim.py's row rule (plant_row), and the trace row holds the state
+// BEFORE the step with the ctrl the step applies.  ONE kernel serves the built-in robot families and the task plugins:
+//   - libdialplant.so (plant_family.hip, one translation unit per robot family) -- never libdialhip.so, whose code objects stay as
+//     shipped; libdialhip.so reaches these launches through the table below (dlopen);
+//   - a task plugin built with a plant (plugin.hip -DDIAL_PLUGIN_PLANT=1): the same kernel at ONE model's compile-time dimensions,
+//     reached through plant_plugin.h's table.
+// Control modes: DIAL_PLANT_CTRL (the row is the ctrl) and DIAL_PLANT_PD (the row is a joint target, act2tau at the plant rate) for
+// every instantiation, and -- a plugin with a user control law only (Dims::user_ctrl; for every built-in Dims the branch vanishes) --
+// DIAL_PLANT_LAW: the row is a normalised action, and lane a evaluates dial_user_control (user_control.h) at EVERY sim step from the
+// plant's current qpos / qvel.  The law's value is the step's ctrl (and the trace's); the actuators apply it as they apply any ctrl.
+// What the law sees beyond user_control.h's list: step = plant_law_step(t, ctrl_dt), dt = (float)ctrl_dt, act = the picked row
+// (global memory), info_user = the state's slots as they are, params = the shared parameters, the table row of that step straight
+// from global memory (no ring: the plant has no reward that would read it after the physics).  Per step the law's control phase
+// issues two kinds of global loads, the row and the table row; everything else the law reads is LDS (the staged constants, the state).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,6 +51,17 @@ __host__ __device__ inline int plant_row(double t, double plan_time, double ctrl
   return (int)q;
 }
 
+// The control step the plant's clock is in, as DIAL_PLANT_LAW hands it to the law (DialControlIn::step): trunc(t / ctrl_dt) with the
+// correctly rounded fp64 quotient (plant_ddiv_rn: the truncation must not depend on the translation unit's flags), 0 when the
+// quotient is not >= 0 (negative clocks, NaN) and capped at 2^24, the last counter a float holds exactly.  Written so that no
+// out-of-range double reaches the int conversion.  deploy/plant.py: law_step restates it on the host.
+__device__ __forceinline__ int plant_law_step(double t, double ctrl_dt) {
+  const double q = plant_ddiv_rn(t, ctrl_dt);
+  if (!(q >= 0.0)) return 0;
+  if (q >= 16777216.0) return 1 << 24;
+  return (int)q;
+}
+
 typedef hipError_t (*dial_plant_launch_fn)(const void* dcm, size_t lds, hipStream_t st, float* states, double* t, const float* plan_time,
                                            const float* ctrl, int T, double ctrl_dt, double sim_dt, int K, int flags, float* trace, int M);
 
@@ -66,21 +89,43 @@ plant_kernel(const CModel<D>* __restrict__ gm, float* states, double* tclk, cons
   float* state = states + (size_t)b * (nq + 2 * nv + DIAL_INFO_N);
   const float* rows = ctrl + (size_t)b * T * nu;
   const bool pd = (flags & DIAL_PLANT_PD) != 0, hold = (flags & DIAL_PLANT_HOLD_FIRST) != 0;
+  const bool law = D::user_ctrl && (flags & DIAL_PLANT_LAW) != 0;
   dial::init_world(w, s);
   dial::init_square(w, m, s);
   dial::load_state(w, m, s, state);
   double t = tclk[b];   // (wave-uniform: every lane runs the same fp64 clock)
   const double pt = (double)plan_time[b];
+  const float cdt = (float)ctrl_dt;
   for (int k = 0; k < K; k++) {
     const float* row = rows + (size_t)(hold ? 0 : plant_row(t, pt, ctrl_dt, T)) * nu;
-    w.items(nu, [&](int a) {
-      float c = row[a];
-      if (pd) {   // act2tau (base_env.py:53-66) on the joint target itself, at the plant rate
-        const float q_err = c - s.qpos[7 + a];
-        c = dm::clip(m->kp[a] * q_err - m->kd[a] * s.qvel[6 + a], m->tau_range[a][0], m->tau_range[a][1]);
+    bool done = false;
+    if constexpr (D::user_ctrl) {
+      if (law) {
+        // once per step and a scalar: the table's row index (an integer modulo under DIAL_TABLE_WRAP) is computed on it
+        const int step = __builtin_amdgcn_readfirstlane(plant_law_step(t, ctrl_dt));
+        const float* trow = nullptr;
+        int tindex = 0;
+        if (m->table_rows > 0) {
+          tindex = dial::table_row_index(step, m->table_row0, m->table_rows, m->table_mode);
+          trow = m->table + (size_t)tindex * m->table_cols;
+        }
+        w.items(nu, [&](int a) {
+          DialControlIn in = dial::control_in(m, (float)step, s.qpos, s.qvel, row, trow, tindex);
+          in.dt = cdt;   // (the constants' dt is the plant context's: sim_dt)
+          s.ctrl[a] = dial_user_control(in, a, m->user_params, s.info + DIAL_INFO_USER);
+        });
+        done = true;
       }
-      s.ctrl[a] = c;
-    });
+    }
+    if (!done)
+      w.items(nu, [&](int a) {
+        float c = row[a];
+        if (pd) {   // act2tau (base_env.py:53-66) on the joint target itself, at the plant rate
+          const float q_err = c - s.qpos[7 + a];
+          c = dm::clip(m->kp[a] * q_err - m->kd[a] * s.qvel[6 + a], m->tau_range[a][0], m->tau_range[a][1]);
+        }
+        s.ctrl[a] = c;
+      });
     if (trace) {   // dial_sim.py's record row: the state BEFORE the step and the ctrl the step applies
       float* tr = trace + ((size_t)b * K + k) * W;
       const float tf = (float)t;

@@ -7,8 +7,9 @@
 //   dial_user_control.hip the user's definition of dial_user_control (user_control.h states the contract)
 // Such a plugin carries one more kernel, user_control_kernel, and exports a second table (plugin_ops.h: dial_plugin_ctrl).
 // Every plugin exports a third, dial_plugin_table (the reference table of dial_set_user_table: host code only, no kernel).
-// A plugin built with a plant (-DDIAL_PLUGIN_PLANT=1) carries plant_user_kernel and exports a fourth, dial_plugin_plant
-// (plant_plugin.h: dial_plant_step on the plugin's contexts).
+// A plugin built with a plant (-DDIAL_PLUGIN_PLANT=1) carries plant_kernel<DimsPlugin> (plant_kernel.h: the kernel of the built-in
+// families, with the law as a third control mode) and exports a fourth, dial_plugin_plant (plant_plugin.h: dial_plant_step on the
+// plugin's contexts).
 #include "plugin_ops.h"
 #ifndef DIAL_PLUGIN_PLANT
 #define DIAL_PLUGIN_PLANT 0
@@ -61,8 +62,8 @@ extern "C" __attribute__((visibility("default"))) const dial_plugin_ctrl* dial_p
 #endif
 
 #if DIAL_PLUGIN_PLANT
-template __global__ void plant_user_kernel<DimsPlugin>(const CModel<DimsPlugin>*, float*, double*, const float*, const float*, int, double, double,
-                                                        int, int, float*);
+template __global__ void plant_kernel<DimsPlugin>(const CModel<DimsPlugin>*, float*, double*, const float*, const float*, int, double, double,
+                                                   int, int, float*);
 
 extern "C" __attribute__((visibility("default"))) const dial_plugin_plant* dial_plugin_plant_v1(void) {
   return PluginPlant<DimsPlugin>::table();

@@ -37,7 +37,7 @@ def sync_steps(t: float, plan_time, ctrl_dt: float, sim_dt: float) -> int:
 
 
 def law_step(t: float, ctrl_dt: float) -> int:
-    """The control step the clock t is in, as DIAL_PLANT_LAW hands it to a custom env's control law (csrc/plant_plugin.h:
+    """The control step the clock t is in, as DIAL_PLANT_LAW hands it to a custom env's control law (csrc/plant_kernel.h:
     plant_law_step): the fp64 quotient t / ctrl_dt truncated toward zero, 0 when the quotient is not >= 0 (negative clocks, NaN),
     at most 2^24."""
     q = float(t) / float(ctrl_dt)
@@ -53,7 +53,8 @@ class Plant:
     (DIAL_PLANT_CTRL, dial_sim.py's ``data.ctrl = tau_shared[k]``); "position" -- the rows are joint targets, turned into torques by
     the env's PD law at every sim step (DIAL_PLANT_PD), or, on models whose actuators are position actuators (the Allegro), handed to
     them as their ctrl (DIAL_PLANT_CTRL).  A custom environment (envs/custom_env.py) is stepped by the plant kernel of its own task
-    plugin (csrc/plant_plugin.h); "position" there needs the PD law's joint indexing (torque_joint_convention), and an env with a
+    plugin (csrc/plant_kernel.h at the model's dimensions, behind csrc/plant_plugin.h's table); "position" there needs the PD law's
+    joint indexing (torque_joint_convention), and an env with a
     control law (control_hip) has a third mode, "law": the rows are normalised actions and the law runs at every sim step from the
     plant's current state (DIAL_PLANT_LAW; law_step is the step counter it sees)."""
 

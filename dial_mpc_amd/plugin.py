@@ -7,7 +7,8 @@ compiles that one translation unit with the product flags (``_lib._COMMON + _FAS
 ``csrc/user_reward.h``.  ``control_src`` adds a control law (contract: ``csrc/user_control.h``) in place of BaseEnv's act2joint /
 PD law; such a plugin carries one more kernel (``user_control_kernel``) and exports a second symbol (``CTRL_SYMBOL``).  Every plugin
 exports ``TABLE_SYMBOL``, the host function behind the reference table (``dial_set_user_table``; no kernel of its own).
-``plant=True`` adds the plant simulator's kernel at the model's dimensions (``csrc/plant_plugin.h``: ``plant_user_kernel``,
+``plant=True`` adds the plant simulator's kernel at the model's dimensions (``plant_kernel`` of ``csrc/plant_kernel.h``,
+the built-in families' kernel, behind the table of ``csrc/plant_plugin.h``;
 ``dial_plant_step`` on the plugin's contexts) and a fourth symbol (``PLANT_SYMBOL``); a plugin built without it is unchanged.  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
 hashes every csrc source, ``include/dial_mpc.h``, the reward, the control law (when there is one), the dimensions, the flags and ``hipcc --version``.  hipcc
 cross-compiles, so building needs no GPU.

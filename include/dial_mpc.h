@@ -600,7 +600,8 @@ int dial_set_user_table(dial_ctx* ctx, const float* table, int rows, int cols, i
  * DIAL_PLANT_PD: ctrl = clip(kp (row - q) - kd qd, tau_range) at every step, kp / kd / tau_range of the task (act2tau without
  * act2joint); refused on models with position actuators.
  * Task-plugin contexts (dial_create_plugin) are served by the plugin's own plant kernel when the plugin was built with one
- * (build_plugin(plant=True): the optional table dial_plugin_plant_v1, csrc/plant_plugin.h), with the same arguments and rules;
+ * (build_plugin(plant=True): the optional table dial_plugin_plant_v1 of csrc/plant_plugin.h, the kernel csrc/plant_kernel.h's), with
+ * the same arguments and rules;
  * DIAL_PLANT_PD there needs actuator a on qpos[7 + a] / dof 6 + a after a free base joint.  Such a plugin with a user control law
  * adds DIAL_PLANT_LAW: the row is a normalised action in [-1, 1] and the law (csrc/user_control.h) runs at EVERY sim step from the
  * plant's current qpos / qvel; its value is the step's ctrl (and the trace's), applied by the actuators like any ctrl.  The law

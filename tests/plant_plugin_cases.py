@@ -1,5 +1,6 @@
 """Shared pieces of the plant-plugin tests (tests/test_plant_plugin.py on the CPU, tests/test_gpu_plant_plugin.py on the GPU): task
-plugins built WITH the plant simulator's kernel (build_plugin(plant=True), csrc/plant_plugin.h) for two models of
+plugins built WITH the plant simulator's kernel (build_plugin(plant=True): csrc/plant_kernel.h's plant_kernel behind
+csrc/plant_plugin.h's table) for two models of
 tests/plugin_cases.py -- the Go2 and the H1 push-crate scene (nu = 19, a dry-friction row, the generic feature set) -- each without a
 law and with the probe law of tests/control_probe.hip, next to the probe reward of tests/plugin_probe.hip; the Go2 also with the
 table probe of tests/plant_law_probe.hip and as a plugin whose plant table reports another version."""

@@ -1,5 +1,6 @@
 """GPU tests of the plant simulator of custom environments: dial_plant_step on contexts of task plugins built with plant=True
-(csrc/plant_plugin.h: plant_user_kernel) -- DIAL_PLANT_CTRL / DIAL_PLANT_PD against the fp32 oracle on the Go2 and the H1 push-crate
+(csrc/plant_kernel.h: plant_kernel at the plugin's Dims, behind csrc/plant_plugin.h's table) -- DIAL_PLANT_CTRL / DIAL_PLANT_PD
+against the fp32 oracle on the Go2 and the H1 push-crate
 scene, DIAL_PLANT_LAW (the plugin's control law at every sim step) against the oracle's built-in PD law, the law's inputs bit for
 bit through the trace's ctrl columns, the bit identities of all three modes, the refusals, and the go2_height_walk example in a
 closed loop with the planner -- in one process and as dial-mpc-sim2sim."""

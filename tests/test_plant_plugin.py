@@ -1,5 +1,6 @@
 """The plant simulator of custom environments without a GPU: a task plugin built with plant=True cross-compiles with exactly one more
-kernel (plant_user_kernel) and a fourth table, with and without a control law; a plugin built without the flag stays as it was; the
+kernel (plant_kernel at the plugin's Dims: the kernel of the built-in families, csrc/plant_kernel.h) and a fourth table, with and
+without a control law; a plugin built without the flag stays as it was; the
 Python surface (the DIAL_PLANT_LAW flag, deploy.plant.law_step, Plant's argument errors that need no device)."""
 import ctypes
 import math
@@ -51,7 +52,8 @@ def test_plant_plugin_has_one_more_kernel_and_the_fourth_table(plugins, model, l
     assert len(cos) == 1
     count = lambda k: sum(k + "I8DimsUser" in n for n in names)   # noqa: E731
     assert count("rollout_kernel") == 3 and count("env_step_kernel") == 1 and count("env_reset_kernel") == 1, names
-    assert count("plant_user_kernel") == 1 and count("user_control_kernel") == (1 if law else 0), names
+    assert count("plant_kernel") == 1 and count("user_control_kernel") == (1 if law else 0), names
+    assert not any("plant_user_kernel" in n for n in names), names   # (one plant kernel: no copy of it under a name of the plugin's)
     assert len(names) == len(set(names)) == (7 if law else 6), names
     h = ctypes.CDLL(so, mode=ctypes.RTLD_LOCAL)
     entry = getattr(h, PLANT_SYMBOL)

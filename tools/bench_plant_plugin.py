@@ -1,5 +1,5 @@
-"""Latency and throughput of the plant simulator of a custom environment (csrc/plant_plugin.h: plant_user_kernel in the env's task
-plugin) next to the built-in plant kernels, on one GPU; writes profiles/plant_plugin.md.  Modelled on tools/bench_plant.py.
+"""Latency and throughput of the plant simulator of a custom environment (csrc/plant_kernel.h: plant_kernel at the model's dimensions in the env's
+task plugin) next to the built-in plant kernels, on one GPU; writes profiles/plant_plugin.md.  Modelled on tools/bench_plant.py.
 
   async step   one sim step of one plant (M = 1, K = 1), including the [qpos, qvel] copy to the host
   batch        M = 256 plants x K = 4 steps per launch, in plant steps per second
@@ -36,7 +36,7 @@ PATHS = ("plugin CTRL", "plugin LAW", "Go2 kernel", "capacity")
 
 
 def kernel_resources(model_name):
-    """{field: value} of plant_user_kernel in the plant-enabled probe plugin (with the probe law) of a model of tests/plugin_cases.py."""
+    """{field: value} of plant_kernel<DimsUser...> in the plant-enabled probe plugin (with the probe law) of a model of tests/plugin_cases.py."""
     from control_cases import control_source
     from dial_mpc_amd import plugin
     from dial_mpc_amd._lib import _COMMON, _CSRC, _FAST
@@ -58,10 +58,10 @@ def kernel_resources(model_name):
             cur = m.group(1)
             continue
         m = re.search(r"remark:\s+([A-Za-z][A-Za-z ]*?)(?: \[[^\]]*\])?: (\S+)$", line)
-        if m and cur and "plant_user_kernel" in cur:
+        if m and cur and "plant_kernel" in cur:
             out[m.group(1).strip()] = m.group(2)
     if not out:
-        raise RuntimeError("no kernel-resource-usage remark names plant_user_kernel:\n" + r.stdout[-2000:])
+        raise RuntimeError("no kernel-resource-usage remark names plant_kernel:\n" + r.stdout[-2000:])
     return out
 
 
@@ -166,7 +166,7 @@ def main():
         where = "between the Go2's own kernel and the capacity-dimension kernel, as expected" if lo <= r <= hi else (
             "NOT between the two built-in kernels: it is " + ("slower than both" if r < lo else "faster than both"))
         lines.append(f"Batch throughput of {k}: {where}.")
-    lines += ["", "## plant_user_kernel: registers, spills, scratch (-Rpass-analysis=kernel-resource-usage, plugin with the probe law)", ""]
+    lines += ["", "## plant_kernel<DimsUser...>: registers, spills, scratch (-Rpass-analysis=kernel-resource-usage, plugin with the probe law)", ""]
     fields = [f for f in ("VGPRs", "AGPRs", "TotalSGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize", "Occupancy", "LDS Size") if
               all(f in res[n] for n in res)]
     lines += ["| model | " + " | ".join(fields) + " |", "|---" * (len(fields) + 1) + "|"]
