@@ -5,7 +5,10 @@ bookkeeping changed between releases.  What can be pinned without it is what eve
 distance between the two shapes, a normal along which they separate, a contact point between the two surfaces.  These
 tests check the oracle's restatement (oracle/dial_oracle.c: sphere_box, plane_box, capsule_box, box_box) against brute
 force -- SciPy minimisers over the shapes' parametrisations and dense direction sampling of the support functions -- and
-never against the HIP code (tests/test_wave_emu.py and tests/test_gpu_parity.py compare that with the oracle).
+never against the HIP code.  The kernel's copy (csrc/box_collide.h) is compared with the oracle pair by pair: its host emulator
+build at the end of this file and in tests/test_lane_emu.py, the two device builds in tests/test_gpu_lane_cases.py (one lane per
+candidate, gates of tests/lane_ref.py, which imports the brute-force helpers of this file); whole crate-scene rollouts in
+tests/test_wave_emu.py, test_gpu_crate.py and test_gpu_push_crate.py.
 """
 import numpy as np
 import pytest
