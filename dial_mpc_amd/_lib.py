@@ -73,6 +73,7 @@ def build(force: bool = False, verbose: bool = False, ieee: bool = False) -> str
     fast-math rounding (tests/test_gpu_parity.py: test_ieee_build_needs_no_more_witnesses)."""
     if not ieee:   # the plant simulator's kernels: a library of their own next to the product library (build_plant)
         build_plant(force=force, verbose=verbose)
+        build_plant_dist(force=force, verbose=verbose)
     return _build_lib(IEEE_LIB_PATH if ieee else LIB_PATH, [(os.path.join(_CSRC, "dial_hip.hip"), [], "dial_hip.o")] +
                       [(os.path.join(_CSRC, "kern_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []), f"kern_family_{k}.o")
                        for k in range(N_FAMILIES)], force, verbose, ieee)
@@ -88,6 +89,18 @@ def build_plant(force: bool = False, verbose: bool = False) -> str:
     loads it from its own directory on first use.  Same staleness check, lock and parallel compile as `build`."""
     return _build_lib(PLANT_LIB_PATH, [(os.path.join(_CSRC, "plant_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []),
                                         f"plant_family_{k}.o") for k in range(N_PLANT_FAMILIES)], force, verbose, False)
+
+
+PLANT_DIST_LIB_PATH = os.path.join(_CSRC, "libdialplantdist.so")
+
+
+def build_plant_dist(force: bool = False, verbose: bool = False) -> str:
+    """libdialplantdist.so: the disturbed plant kernel (csrc/plant_dist_kernel.h: velocity kicks and actuator errors,
+    dial_set_plant_disturbance) once per robot family (plant_dist_family.hip -DDIAL_FAMILY=k, build_plant's flags), a library of its
+    own so that libdialplant.so's and libdialhip.so's code objects stay as shipped.  libdialhip.so's dial_plant_step loads it from
+    its own directory the first time a launch has a disturbance bound."""
+    return _build_lib(PLANT_DIST_LIB_PATH, [(os.path.join(_CSRC, "plant_dist_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []),
+                                             f"plant_dist_family_{k}.o") for k in range(N_PLANT_FAMILIES)], force, verbose, False)
 
 
 def _build_lib(out: str, units, force: bool, verbose: bool, ieee: bool) -> str:
@@ -215,6 +228,11 @@ def load(path: Optional[str] = None):
     except AttributeError:
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack the plant simulator)
             raise
+    try:
+        lib.dial_set_plant_disturbance.argtypes = [vp, fp, ci, ci]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack plant disturbances)
+            raise
     lib.dial_env_reset.argtypes = [vp, fp, fp, fp, fp, fp, vp]
     lib.dial_env_reset_batch.argtypes = [vp, fp, fp, fp, fp, fp, ci, vp]
     lib.dial_status.argtypes = [vp]
@@ -242,11 +260,17 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
             "dial_status", "dial_set_timing", "dial_get_rollout_ms", "dial_abi_sizes",
             "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch",
             "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params", "dial_plant_step", "dial_user_control",
-            "dial_set_user_table")
+            "dial_set_user_table", "dial_set_plant_disturbance")
 
 # dial_plant_step flags (include/dial_mpc.h)
 PLANT_CTRL, PLANT_PD, PLANT_HOLD_FIRST = (_abi.MACROS[k] for k in ("DIAL_PLANT_CTRL", "DIAL_PLANT_PD", "DIAL_PLANT_HOLD_FIRST"))
 PLANT_LAW = _abi.MACROS["DIAL_PLANT_LAW"]   # a task plugin built with a plant and a control law: the rows are normalised actions
+PLANT_MAX_EVENTS = _abi.MACROS["DIAL_PLANT_MAX_EVENTS"]   # event slots of a plant's disturbance row (dial_set_plant_disturbance)
+
+
+def plant_dist_row(nu: int, nv: int, n_events: int) -> int:
+    """Floats of one plant's disturbance row, gain[nu] | bias[nu] | E x { t0, t1, dv[nv] } (DIAL_PLANT_DIST_ROW of include/dial_mpc.h)."""
+    return 2 * int(nu) + int(n_events) * (2 + int(nv))
 
 
 def plan_param_rows(rows) -> np.ndarray:
@@ -515,6 +539,25 @@ class Context:
         self._check(self.lib.dial_plant_step(self.h, _ptr(states), t.data_ptr(), _ptr(plan_time), _ptr(ctrl), int(ctrl.shape[1]),
                                              float(ctrl_dt), float(sim_dt), int(K), int(flags), _ptr(trace), M, _stream()),
                     "dial_plant_step")
+
+    def set_plant_disturbance(self, dist, n_events: int = 0):
+        """Bind plant disturbances (dial_set_plant_disturbance): `dist` a contiguous float32 device tensor [M, plant_dist_row(nu, nv,
+        n_events)] -- row m = gain[nu] | bias[nu] | n_events x { t0, t1, dv[nv] } of plant m (deploy/plant.py: disturbance_row packs
+        one) -- bound as it is: the context keeps a reference, and the tensor may be rewritten in place between launches.  While bound,
+        plant_step needs M == dist.shape[0] and runs the disturbed kernel.  None unbinds."""
+        if dist is None:
+            self._check(self.lib.dial_set_plant_disturbance(self.h, None, 0, 0), "dial_set_plant_disturbance")
+            self._plant_dist = None
+            return None
+        n_events = int(n_events)
+        row = plant_dist_row(self.nu, self.nv, n_events)
+        if 0 <= n_events <= PLANT_MAX_EVENTS and (dist.dim() != 2 or int(dist.shape[1]) != row):   # (a bad n_events: the library's message)
+            raise ValueError(f"plant disturbance: rows of {row} floats (2 nu + n_events (2 + nv)) are needed; got shape {tuple(dist.shape)}")
+        if dist.device != self.torch_device:
+            raise ValueError("plant disturbance: the tensor must be on the context's device")
+        self._check(self.lib.dial_set_plant_disturbance(self.h, _ptr(dist), int(dist.shape[0]), n_events), "dial_set_plant_disturbance")
+        self._plant_dist = dist
+        return dist
 
     # ---- K3
     def rollout(self, state, us, want_states: bool = True):

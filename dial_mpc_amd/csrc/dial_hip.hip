@@ -24,6 +24,7 @@
 #include "kernel_list.h"
 #include "plant_kernel.h"
 #include "plant_plugin.h"
+#include "plant_dist_kernel.h"
 #include "plugin_ops.h"
 
 // the kernels are compiled in their own translation units, one per robot family (kern_family.hip, built in parallel)
@@ -352,6 +353,9 @@ struct dial_ctx {
   const dial_plugin_ctrl* plug_ctrl = nullptr;   // inst 7: the plugin's user control law (dial_user_control), nullptr when it has none
   const dial_plugin_table* plug_table = nullptr; // inst 7: the plugin's reference-table function (dial_set_user_table), nullptr: an older plugin
   const dial_plugin_plant* plug_plant = nullptr; // inst 7: the plugin's plant kernel (dial_plant_step), nullptr: built without one
+  const dial_plugin_plant_dist* plug_plant_dist = nullptr;   // inst 7: the plugin's disturbed plant kernel, nullptr: built without one
+  const float* plant_dist = nullptr;       // plant disturbances (dial_set_plant_disturbance), caller-owned device rows ...
+  int plant_dist_M = 0, plant_dist_E = 0;  // ... [plant_dist_M, DIAL_PLANT_DIST_ROW(nu, nv, plant_dist_E)]; nullptr: the undisturbed plant
   std::vector<char> plug_cm;               // inst 7: host copy of the constants (dial_set_user_params rewrites the parameters)
   const float* plan_params = nullptr;      // inst 7: per-plan task parameters (dial_set_plan_params), caller-owned device rows ...
   int plan_rows = 0;                       // ... [plan_rows, DIAL_USER_PARAMS]; nullptr: every launch reads the shared ones
@@ -425,7 +429,7 @@ static int fail(dial_ctx* ctx, int code, const std::string& msg) {
       return fail(ctx, DIAL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
   } while (0)
 
-// dial_create_plugin: an OPTIONAL table of a task plugin (dial_plugin_ctrl / dial_plugin_table / dial_plugin_plant; `what` is its name in the messages):
+// dial_create_plugin: an OPTIONAL table of a task plugin (dial_plugin_ctrl / dial_plugin_table / dial_plugin_plant[_dist]; `what` is its name in the messages):
 // *tab stays nullptr when the plugin does not export `symbol`; a symbol that returns no table, or a table of another version, is an
 // error.  The sizes and dimensions each table records are the caller's to compare.
 template <class Tab>
@@ -529,8 +533,13 @@ int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task*
   if (pla && (pla->cmodel_bytes != ops->cmodel_bytes || pla->sizeof_control_in != sizeof(DialControlIn) || pla->nq != model->nq || pla->nv != model->nv ||
               pla->nu != model->nu || (pla->has_law != 0) != (ctl != nullptr) || !pla->launch))
     return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's plant table was built against another version of the library (ABI mismatch; rebuild it)");
+  // the disturbed plant kernel's table: a fifth symbol, exported only by a plugin built with build_plugin(plant_disturbance=True)
+  const dial_plugin_plant_dist* pld;
+  if (int rc = plugin_table(h, plugin_path, DIAL_PLUGIN_PLANT_DIST_SYMBOL, "plant-disturbance table", DIAL_PLUGIN_PLANT_DIST_VERSION, &pld)) return rc;
+  if (pld && (!pla || pld->cmodel_bytes != ops->cmodel_bytes || pld->nq != model->nq || pld->nv != model->nv || pld->nu != model->nu || !pld->launch))
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's plant-disturbance table was built against another version of the library (ABI mismatch; rebuild it)");
   const int rc = create_impl(out, model, task, cfg, device, -1, opts, ops, params, n_params);
-  if (rc == DIAL_OK) { (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; (*out)->plug_plant = pla; }
+  if (rc == DIAL_OK) { (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; (*out)->plug_plant = pla; (*out)->plug_plant_dist = pld; }
   return rc;
 }
 
@@ -1586,7 +1595,84 @@ static const PlantLib& plant_lib() {
   static const PlantLib lib = plant_load();   // (once per process, thread-safe initialisation)
   return lib;
 }
+// libdialplantdist.so (plant_dist_family.hip): the disturbed plant kernels, looked up the same way the first time a disturbance is bound
+struct PlantDistLib {
+  const dial_plant_dist_ops* ops = nullptr;
+  std::string err;
+};
+static PlantDistLib plant_dist_load() {
+  PlantDistLib r;
+  Dl_info info{};
+  std::string dir = ".";
+  if (dladdr((const void*)&plant_dist_load, &info) && info.dli_fname) {
+    dir = info.dli_fname;
+    const size_t slash = dir.rfind('/');
+    dir = slash == std::string::npos ? "." : dir.substr(0, slash);
+  }
+  const std::string path = dir + "/libdialplantdist.so";
+  void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);   // (never dlclose'd: the runtime holds its code objects)
+  if (!h) { r.err = "cannot load " + path + " (build it: dial_mpc_amd._lib.build()): " + dlerror(); return r; }
+  dial_plant_dist_entry entry = (dial_plant_dist_entry)dlsym(h, DIAL_PLANT_DIST_SYMBOL);
+  const dial_plant_dist_ops* o = entry ? entry() : nullptr;
+  if (!o) r.err = path + " does not export " DIAL_PLANT_DIST_SYMBOL;
+  else if (o->abi_version != DIAL_PLANT_DIST_ABI_VERSION || o->sizeof_model != sizeof(dial_model) || o->sizeof_task != sizeof(dial_task))
+    r.err = path + " was built against another version of the library (rebuild it)";
+  else r.ops = o;
+  return r;
+}
+static const PlantDistLib& plant_dist_lib() {
+  static const PlantDistLib lib = plant_dist_load();   // (once per process, thread-safe initialisation)
+  return lib;
+}
 #endif
+
+// The disturbed kernel's launch function of a context: the plugin's fifth table, or libdialplantdist.so's entry of the context's
+// instantiation.  nullptr with the reason in `why` (DIAL_ERR_UNSUPPORTED).
+static dial_plant_dist_launch_fn plant_dist_launch_of(dial_ctx* ctx, std::string& why) {
+#ifdef DIAL_IEEE_BUILD
+  (void)ctx;
+  why = "the IEEE measurement build carries no plant (use the product library)";
+  return nullptr;
+#else
+  if (ctx->plug) {
+    if (!ctx->plug_plant_dist) {
+      why = "the context's task plugin does not export " DIAL_PLUGIN_PLANT_DIST_SYMBOL " (build it with build_plugin(plant_disturbance=True); "
+            "CustomEnv.make_plant(disturbance=True) does)";
+      return nullptr;
+    }
+    return ctx->plug_plant_dist->launch;
+  }
+  const PlantDistLib& lib = plant_dist_lib();
+  if (!lib.ops) { why = lib.err; return nullptr; }
+  if (ctx->inst < 0 || ctx->inst >= DIAL_PLANT_INSTS || lib.ops->cmodel_bytes[ctx->inst] != ctx->dcm_bytes) {
+    why = "libdialplantdist.so does not match this library's constants (rebuild both)";
+    return nullptr;
+  }
+  return lib.ops->launch[ctx->inst];
+#endif
+}
+
+int dial_set_plant_disturbance(dial_ctx* ctx, const float* dist, int M, int n_events) {
+  if (!ctx) return fail(nullptr, DIAL_ERR_ARG, "dial_set_plant_disturbance: null context");
+  if (n_events < 0 || n_events > DIAL_PLANT_MAX_EVENTS)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plant_disturbance: n_events = " + std::to_string(n_events) + " is outside 0 .. DIAL_PLANT_MAX_EVENTS");
+  if (!dist) {
+    if (M != 0 || n_events != 0)
+      return fail(ctx, DIAL_ERR_ARG, "dial_set_plant_disturbance: a null buffer with M = " + std::to_string(M) + ", n_events = " + std::to_string(n_events) +
+                                     " (NULL with M = n_events = 0 unbinds)");
+    ctx->plant_dist = nullptr;
+    ctx->plant_dist_M = ctx->plant_dist_E = 0;
+    return DIAL_OK;
+  }
+  if (M < 1 || M > DIAL_MAX_PLANTS)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plant_disturbance: M = " + std::to_string(M) + " is outside 1 .. DIAL_MAX_PLANTS");
+  std::string why;
+  if (!plant_dist_launch_of(ctx, why)) return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_set_plant_disturbance: " + why);
+  ctx->plant_dist = dist;
+  ctx->plant_dist_M = M;
+  ctx->plant_dist_E = n_events;
+  return DIAL_OK;
+}
 
 int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_time, const float* ctrl, int T, double ctrl_dt,
                     double sim_dt, int K, int flags, float* trace, int M, void* stream) {
@@ -1629,6 +1715,19 @@ int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_t
   (void)trace; (void)stream;
   return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: the IEEE measurement build carries no plant (use the product library)");
 #else
+  if (ctx->plant_dist) {   // a disturbance is bound (dial_set_plant_disturbance): the disturbed kernel, one row of the buffer per plant
+    if (M != ctx->plant_dist_M)
+      return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: M = " + std::to_string(M) + ", but the bound plant disturbance has " + std::to_string(ctx->plant_dist_M) +
+                                     " rows (dial_set_plant_disturbance)");
+    std::string why;
+    dial_plant_dist_launch_fn dlaunch = plant_dist_launch_of(ctx, why);
+    if (!dlaunch) return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: " + why);
+    if (int rc = check_sticky(ctx)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, dlaunch(ctx->dcm, ctx->lds_bytes, (hipStream_t)stream, states, t, plan_time, ctrl, T, ctrl_dt, sim_dt, K, flags, trace, M, ctx->plant_dist,
+                         ctx->plant_dist_E));
+    return DIAL_OK;
+  }
   dial_plant_launch_fn launch = nullptr;
   if (ctx->plug) launch = ctx->plug_plant->launch;   // the plugin's own plant kernel, at the env.step workspace of the context
   else {

@@ -9,13 +9,23 @@
 // Every plugin exports a third, dial_plugin_table (the reference table of dial_set_user_table: host code only, no kernel).
 // A plugin built with a plant (-DDIAL_PLUGIN_PLANT=1) carries plant_kernel<DimsPlugin> (plant_kernel.h: the kernel of the built-in
 // families, with the law as a third control mode) and exports a fourth, dial_plugin_plant (plant_plugin.h: dial_plant_step on the
-// plugin's contexts).
+// plugin's contexts).  -DDIAL_PLUGIN_PLANT_DIST=1 next to it (build_plugin(plant_disturbance=True)) adds plant_dist_kernel<DimsPlugin>
+// (plant_dist_kernel.h: velocity kicks and actuator errors, dial_set_plant_disturbance) and a fifth table, dial_plugin_plant_dist.
 #include "plugin_ops.h"
 #ifndef DIAL_PLUGIN_PLANT
 #define DIAL_PLUGIN_PLANT 0
 #endif
+#ifndef DIAL_PLUGIN_PLANT_DIST
+#define DIAL_PLUGIN_PLANT_DIST 0
+#endif
+#if DIAL_PLUGIN_PLANT_DIST && !DIAL_PLUGIN_PLANT
+#error "DIAL_PLUGIN_PLANT_DIST needs DIAL_PLUGIN_PLANT"
+#endif
 #if DIAL_PLUGIN_PLANT
 #include "plant_plugin.h"
+#endif
+#if DIAL_PLUGIN_PLANT_DIST
+#include "plant_dist_kernel.h"
 #endif
 #include "dial_plugin_dims.h"
 #include "dial_user_reward.hip"
@@ -67,5 +77,14 @@ template __global__ void plant_kernel<DimsPlugin>(const CModel<DimsPlugin>*, flo
 
 extern "C" __attribute__((visibility("default"))) const dial_plugin_plant* dial_plugin_plant_v1(void) {
   return PluginPlant<DimsPlugin>::table();
+}
+#endif
+
+#if DIAL_PLUGIN_PLANT_DIST
+template __global__ void plant_dist_kernel<DimsPlugin>(const CModel<DimsPlugin>*, float*, double*, const float*, const float*, int, double, double,
+                                                        int, int, float*, const float*, int);
+
+extern "C" __attribute__((visibility("default"))) const dial_plugin_plant_dist* dial_plugin_plant_dist_v1(void) {
+  return PluginPlantDist<DimsPlugin>::table();
 }
 #endif

@@ -8,6 +8,10 @@ Protocol: the six shared-memory segments of dial_plan.py, created here (``open_s
 Async mode: every sim step applies the row of the published plan that the planner's latency selects (plant.ctrl_row), paced at
 sim_dt / real_time_factor of wall time.  Sync mode: after each published plan, the steps up to plan_time + ctrl_dt apply row 0
 (plant.sync_steps), in one launch.
+
+``sim_disturbance`` (optional) disturbs the plant, not the planner's model: an actuator gain / bias (a weak or offset motor) and
+timed shoves of the base (deploy/plant.py: Plant.shove; csrc/plant_dist_kernel.h).  The plant's constants -- masses, inertias,
+friction, geometry -- stay the planner's.
 """
 from __future__ import annotations
 
@@ -17,7 +21,7 @@ import os
 import sys
 import time
 from dataclasses import dataclass
-from typing import Optional
+from typing import Any, Dict, Optional
 
 import numpy as np
 
@@ -35,6 +39,42 @@ class DialSimConfig:
     real_time_factor: float
     sim_dt: float
     sync_mode: bool
+    # plant disturbances (sim_disturbance_settings reads it); None: the undisturbed plant
+    #   {actuator_gain: float | [nu], actuator_bias: float | [nu], shoves: [{t, duration, dv: [6]}], seed: int, gain_range: [lo, hi]}
+    sim_disturbance: Optional[Dict[str, Any]] = None
+
+
+_DISTURBANCE_KEYS = ("actuator_gain", "actuator_bias", "shoves", "seed", "gain_range")
+
+
+def sim_disturbance_settings(block: Dict[str, Any], nu: int):
+    """A `sim_disturbance` block -> (gain [nu], bias [nu], shoves [(t, duration, dv6)]).  actuator_gain / actuator_bias: one value
+    for every actuator or a list of nu; gain_range: [lo, hi] draws one gain per actuator, uniformly, from numpy's default_rng(seed)
+    (seed defaults to 0) and multiplies actuator_gain; shoves: Plant.shove's arguments (dv: the base's total velocity change,
+    [vx, vy, vz] world frame in m/s, [wx, wy, wz] body frame in rad/s).  Raises ValueError on unknown keys and bad shapes."""
+    if not isinstance(block, dict):
+        raise ValueError(f"sim_disturbance is a mapping; got {type(block).__name__}")
+    unknown = sorted(set(block) - set(_DISTURBANCE_KEYS))
+    if unknown:
+        raise ValueError(f"sim_disturbance: unknown keys {unknown}; known: {list(_DISTURBANCE_KEYS)}")
+
+    def per_actuator(key, default):
+        a = np.asarray(block.get(key, default), dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != nu) or not np.isfinite(a).all():
+            raise ValueError(f"sim_disturbance.{key}: one finite value or a list of nu = {nu}; got {block.get(key)!r}")
+        return np.broadcast_to(a, (nu,)).copy()
+    gain, bias = per_actuator("actuator_gain", 1.0), per_actuator("actuator_bias", 0.0)
+    if block.get("gain_range") is not None:
+        r = np.asarray(block["gain_range"], dtype=np.float64)
+        if r.shape != (2,) or not np.isfinite(r).all() or r[0] > r[1]:
+            raise ValueError(f"sim_disturbance.gain_range: [lo, hi] with lo <= hi; got {block['gain_range']!r}")
+        gain = gain * np.random.default_rng(int(block.get("seed") or 0)).uniform(r[0], r[1], nu)
+    shoves = []
+    for i, sh in enumerate(block.get("shoves") or []):
+        if not isinstance(sh, dict) or set(sh) != {"t", "duration", "dv"} or np.asarray(sh["dv"], dtype=np.float64).shape != (6,):
+            raise ValueError(f"sim_disturbance.shoves[{i}]: {{t, duration, dv: [6]}} is needed; got {sh!r}")
+        shoves.append((float(sh["t"]), float(sh["duration"]), np.asarray(sh["dv"], dtype=np.float64)))
+    return gain, bias, shoves
 
 
 class DialSim:
@@ -58,7 +98,15 @@ class DialSim:
         if not os.path.exists(os.path.splitext(scene)[0] + ".json"):
             print(f"[dial-mpc-sim] scene {sim_config.scene_name} is not a compiled scene of this package: simulating the env's own "
                   f"scene ({type(env).__name__}) at sim_dt = {self.sim_dt}")
-        self.plant = Plant(env, self.sim_dt, self.leg_control, M=1, device=device)
+        if sim_config.sim_disturbance is None:
+            self.plant = Plant(env, self.sim_dt, self.leg_control, M=1, device=device)
+        else:
+            gain, bias, shoves = sim_disturbance_settings(sim_config.sim_disturbance, int(env.sys.nu))
+            self.plant = Plant(env, self.sim_dt, self.leg_control, M=1, device=device, disturbance=dict(gain=gain, bias=bias))
+            for t, duration, dv in shoves:
+                self.plant.shove(t, duration, dv)
+            print(f"[dial-mpc-sim] plant disturbance: actuator gain {np.round(gain, 3).tolist()}, bias {np.round(bias, 3).tolist()}, "
+                  f"{len(shoves)} shove(s)")
         self.nq, self.nv, self.nu = self.plant.nq, self.plant.nv, self.plant.nu
         self.default_u = np.zeros(self.nu, np.float32)   # (the compiled scenes' home keyframes carry no ctrl)
         self._seg = open_segments(self.nq, self.nv, self.nu, self.n_acts, create=True, prefix=shm_prefix)

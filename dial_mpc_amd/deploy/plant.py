@@ -4,6 +4,13 @@
 
 ``ctrl_row`` and ``sync_steps`` restate those rules on the host in fp64; the kernel picks its rows with the same arithmetic and the
 GPU tests compare the two bit for bit.
+
+Plant disturbances (``dial_set_plant_disturbance``, csrc/plant_dist_kernel.h): per plant, timed velocity kicks and an actuator
+gain / bias.  ``event_fires`` restates the kernel's window test, ``disturbance_row`` packs one plant's row, and ``Plant`` binds
+them (``Plant(..., disturbance=)``, ``set_disturbance``, ``shove``).  A kick's ``dv`` is in generalised velocity coordinates and
+the model's units: behind a free base joint dofs 0-2 are the base's linear velocity in the WORLD frame (m/s), dofs 3-5 its angular
+velocity in the BODY frame (rad/s), the rest joint rates.  The plant's constants stay the planner's: masses, inertias, friction and
+geometry are not disturbed (their derived constants would have to be recompiled through mjcf.py).
 """
 from __future__ import annotations
 
@@ -11,6 +18,8 @@ import math
 from typing import Optional
 
 import numpy as np
+
+from dial_mpc_amd import _abi
 
 
 def ctrl_row(t: float, plan_time, ctrl_dt: float, n_acts: int) -> int:
@@ -48,6 +57,52 @@ def law_step(t: float, ctrl_dt: float) -> int:
     return int(q)
 
 
+MAX_EVENTS = _abi.MACROS["DIAL_PLANT_MAX_EVENTS"]   # event slots of one plant's row (include/dial_mpc.h: 16)
+
+
+def event_fires(t: float, t0, t1) -> bool:
+    """The disturbed kernel's window test: the event with the float32 bounds t0, t1 fires at the sim step whose clock BEFORE the
+    step is t (fp64) when t >= (double)t0 and t < (double)t1.  t1 <= t0 (the all-zero slot) and NaN never fire."""
+    t, a, b = float(t), float(np.float32(t0)), float(np.float32(t1))
+    return bool(t >= a and t < b)
+
+
+def disturbance_row(nu: int, nv: int, gain=None, bias=None, events=None) -> np.ndarray:
+    """One plant's disturbance row as dial_set_plant_disturbance takes it: float32 [2 nu + E (2 + nv)] =
+    gain[nu] | bias[nu] | E x { t0, t1, dv[nv] }.  gain / bias: a scalar or [nu] (None: 1 / 0, the perfect actuator); events: a
+    list of (t0, t1, dv[nv]), applied in this order, E = len(events) <= 16 (pad with (0, 0, zeros) for a common E: that slot
+    never fires).  Raises ValueError on non-finite values, other shapes or more than 16 events."""
+    nu, nv = int(nu), int(nv)
+    events = [] if events is None else list(events)
+    if len(events) > MAX_EVENTS:
+        raise ValueError(f"{len(events)} events; a plant's disturbance row holds at most DIAL_PLANT_MAX_EVENTS = {MAX_EVENTS}")
+
+    def per_actuator(x, default, what):
+        a = np.asarray(default if x is None else x, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != nu):
+            raise ValueError(f"actuator {what}: a scalar or [nu = {nu}] values; got shape {a.shape}")
+        a = np.broadcast_to(a, (nu,)).astype(np.float32)
+        if not np.isfinite(a).all():
+            raise ValueError(f"actuator {what}: non-finite value")
+        return a
+    row = np.zeros(2 * nu + len(events) * (2 + nv), np.float32)
+    row[:nu] = per_actuator(gain, 1.0, "gain")
+    row[nu:2 * nu] = per_actuator(bias, 0.0, "bias")
+    for e, ev in enumerate(events):
+        if len(ev) != 3:
+            raise ValueError(f"event {e}: (t0, t1, dv[nv]) is needed; got {len(ev)} items")
+        t0, t1, dv = ev
+        dv = np.asarray(dv, dtype=np.float64)
+        if dv.shape != (nv,):
+            raise ValueError(f"event {e}: dv has shape {dv.shape}; [nv = {nv}] generalised velocities are needed")
+        slot = np.concatenate([[float(t0), float(t1)], dv]).astype(np.float32)
+        if not np.isfinite(slot).all():
+            raise ValueError(f"event {e}: non-finite window or dv")
+        o = 2 * nu + e * (2 + nv)
+        row[o:o + 2 + nv] = slot
+    return row
+
+
 class Plant:
     """M copies of an env's plant, stepped on the GPU.  ``leg_control``: "torque" -- the rows are the actuators' ctrl as they are
     (DIAL_PLANT_CTRL, dial_sim.py's ``data.ctrl = tau_shared[k]``); "position" -- the rows are joint targets, turned into torques by
@@ -58,7 +113,9 @@ class Plant:
     control law (control_hip) has a third mode, "law": the rows are normalised actions and the law runs at every sim step from the
     plant's current state (DIAL_PLANT_LAW; law_step is the step counter it sees)."""
 
-    def __init__(self, env, sim_dt: float, leg_control: str = "torque", M: int = 1, device: Optional[int] = None):
+    def __init__(self, env, sim_dt: float, leg_control: str = "torque", M: int = 1, device: Optional[int] = None, disturbance=None):
+        """disturbance: None (the undisturbed plant, the context and kernels as they were), True (a context that can take
+        disturbances: set_disturbance / shove later) or a dict of set_disturbance's arguments (gain, bias, events), bound at once."""
         import torch
         from dial_mpc_amd import _lib
         from dial_mpc_amd.envs.custom_env import CustomEnv, torque_joint_convention
@@ -80,15 +137,97 @@ class Plant:
         self.env, self.sim_dt, self.M = env, float(sim_dt), int(M)
         self.ctrl_dt = float(env._config.dt)
         self._hold = _lib.PLANT_HOLD_FIRST
-        self.ctx = env.make_plant(self.sim_dt, device=device)
+        self._dist_capable = disturbance is not None and disturbance is not False
+        self.ctx = env.make_plant(self.sim_dt, device=device, disturbance=True) if self._dist_capable else env.make_plant(self.sim_dt, device=device)
         self.nq, self.nv, self.nu = self.ctx.nq, self.ctx.nv, self.ctx.nu
         self.width = 1 + self.nq + self.nv + self.nu          # trace / record row: [t, qpos, qvel, ctrl]
         self.dev = self.ctx.torch_device
         self._torch = torch
+        self._gain = self._bias = None       # [M, nu] float32, or None: 1 / 0
+        self._events = [[] for _ in range(self.M)]   # per plant: (t0, t1, dv[nv]) in firing order
+        self._dist = None                    # the bound device tensor
         self.reset()
+        if isinstance(disturbance, dict):
+            self.set_disturbance(**disturbance)
+
+    # ---- disturbances (dial_set_plant_disturbance)
+    def _per_plant(self, x, what):
+        a = np.asarray(x, dtype=np.float64)
+        if a.ndim > 2 or (a.ndim >= 1 and a.shape[-1] != self.nu) or (a.ndim == 2 and a.shape[0] != self.M):
+            raise ValueError(f"actuator {what}: a scalar, [nu = {self.nu}] or [M = {self.M}, nu] values; got shape {a.shape}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"actuator {what}: non-finite value")
+        return np.broadcast_to(a, (self.M, self.nu)).astype(np.float32)
+
+    def set_disturbance(self, gain=None, bias=None, events=None):
+        """Replace the plants' disturbances and bind them.  gain / bias: a scalar, [nu] (every plant) or [M, nu]; None: 1 / 0.
+        events: a list of (plant or None, t0, t1, dv[nv]) -- plant None: every plant -- fired in list order, at most 16 per plant
+        (see disturbance_row; the windows are on the plant's own clock, which reset() sets to 0).  All three None: unbind, the
+        undisturbed kernel runs again.  Needs Plant(..., disturbance=True or a dict)."""
+        if not self._dist_capable:
+            raise ValueError("this Plant was created without disturbances: pass disturbance=True (or a dict of gain / bias / events) to Plant")
+        if gain is None and bias is None and events is None:
+            self._gain = self._bias = None
+            self._events = [[] for _ in range(self.M)]
+            self._dist = self.ctx.set_plant_disturbance(None)
+            return None
+        self._gain = None if gain is None else self._per_plant(gain, "gain")
+        self._bias = None if bias is None else self._per_plant(bias, "bias")
+        per = [[] for _ in range(self.M)]
+        for ev in (events or []):
+            if len(ev) != 4:
+                raise ValueError(f"an event is (plant or None, t0, t1, dv[nv]); got {len(ev)} items")
+            m, t0, t1, dv = ev
+            if m is not None and not 0 <= int(m) < self.M:
+                raise ValueError(f"event for plant {m}; this Plant has M = {self.M}")
+            for k in (range(self.M) if m is None else [int(m)]):
+                per[k].append((t0, t1, dv))
+        self._events = per
+        return self._bind()
+
+    def _bind(self):
+        E = max(len(p) for p in self._events)
+        pad = (0.0, 0.0, np.zeros(self.nv))   # (t1 <= t0: never fires)
+        rows = np.stack([disturbance_row(self.nu, self.nv, None if self._gain is None else self._gain[m],
+                                         None if self._bias is None else self._bias[m], self._events[m] + [pad] * (E - len(self._events[m])))
+                         for m in range(self.M)])
+        self._dist = self.ctx.set_plant_disturbance(self._torch.as_tensor(rows, device=self.dev), E)
+        return self._dist
+
+    def shove(self, t: float, duration: float, dvel6, plant: Optional[int] = None):
+        """Shove the base: over the sim steps whose clocks lie in [t, t + duration) the base's velocity changes by dvel6 IN ALL --
+        [vx, vy, vz] in the world frame (m/s), [wx, wy, wz] in the body frame (rad/s) -- in n = max(1, round(duration / sim_dt))
+        equal per-step increments dvel6 / n (float32), as one more event of `plant` (None: every plant) after those already there.
+        The window is [t - sim_dt / 2, t - sim_dt / 2 + n sim_dt): accumulated clocks land next to multiples of sim_dt on either
+        side, and the half step keeps exactly n of them inside.  Needs a free base joint.  Returns (t0, t1, dv) as bound."""
+        m = self.env.sys.model
+        if not (int(m["njnt"]) > 0 and int(np.asarray(m["jnt_type"]).ravel()[0]) == 0 and self.nv >= 6):
+            raise ValueError("shove needs a free base joint (dofs 0-5 of the model): this model has none; use set_disturbance(events=) "
+                             "with a dv in the model's own coordinates")
+        d6 = np.asarray(dvel6, dtype=np.float64)
+        if d6.shape != (6,) or not np.isfinite(d6).all():
+            raise ValueError(f"shove: dvel6 is [vx, vy, vz, wx, wy, wz], finite; got shape {d6.shape}")
+        if not (math.isfinite(t) and math.isfinite(duration) and duration >= 0.0):
+            raise ValueError("shove: t and duration must be finite, duration >= 0")
+        n = max(1, int(round(float(duration) / self.sim_dt)))
+        dv = np.zeros(self.nv)
+        dv[:6] = d6 / n
+        t0 = float(t) - 0.5 * self.sim_dt
+        ev = (t0, t0 + n * self.sim_dt, dv)
+        if not self._dist_capable:
+            raise ValueError("this Plant was created without disturbances: pass disturbance=True to Plant")
+        if plant is not None and not 0 <= int(plant) < self.M:
+            raise ValueError(f"shove of plant {plant}; this Plant has M = {self.M}")
+        for k in (range(self.M) if plant is None else [int(plant)]):
+            if len(self._events[k]) >= MAX_EVENTS:
+                raise ValueError(f"plant {k} already has {MAX_EVENTS} events (DIAL_PLANT_MAX_EVENTS)")
+            self._events[k].append(ev)
+        self._bind()
+        return (np.float32(ev[0]), np.float32(ev[1]), dv.astype(np.float32))
 
     def reset(self):
-        """Every plant at the env's initial pose (the home keyframe; env.reset's), zero velocity, t = 0."""
+        """Every plant at the env's initial pose (the home keyframe; env.reset's), zero velocity, t = 0.  A bound disturbance stays
+        bound (its windows are on the clock that starts again at 0)."""
         torch = self._torch
         q0 = np.asarray(self.env._init_q, np.float32)
         qpos = torch.as_tensor(np.tile(q0, (self.M, 1)), device=self.dev)

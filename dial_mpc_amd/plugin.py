@@ -9,7 +9,9 @@ PD law; such a plugin carries one more kernel (``user_control_kernel``) and expo
 exports ``TABLE_SYMBOL``, the host function behind the reference table (``dial_set_user_table``; no kernel of its own).
 ``plant=True`` adds the plant simulator's kernel at the model's dimensions (``plant_kernel`` of ``csrc/plant_kernel.h``,
 the built-in families' kernel, behind the table of ``csrc/plant_plugin.h``;
-``dial_plant_step`` on the plugin's contexts) and a fourth symbol (``PLANT_SYMBOL``); a plugin built without it is unchanged.  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
+``dial_plant_step`` on the plugin's contexts) and a fourth symbol (``PLANT_SYMBOL``); a plugin built without it is unchanged.
+``plant_disturbance=True`` (implies ``plant=True``) adds the disturbed plant kernel (``plant_dist_kernel`` of
+``csrc/plant_dist_kernel.h``; ``dial_set_plant_disturbance``) and a fifth symbol (``PLANT_DIST_SYMBOL``).  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
 hashes every csrc source, ``include/dial_mpc.h``, the reward, the control law (when there is one), the dimensions, the flags and ``hipcc --version``.  hipcc
 cross-compiles, so building needs no GPU.
 """
@@ -33,6 +35,7 @@ SYMBOL = "dial_plugin_ops_v1"
 CTRL_SYMBOL = "dial_plugin_ctrl_v1"   # exported only by a plugin built with a control law
 TABLE_SYMBOL = "dial_plugin_table_v1"  # exported by every plugin: the reference table's host function (dial_set_user_table)
 PLANT_SYMBOL = "dial_plugin_plant_v1"  # exported only by a plugin built with plant=True: the plant kernel's table (dial_plant_step)
+PLANT_DIST_SYMBOL = "dial_plugin_plant_dist_v1"  # only with plant_disturbance=True: the disturbed plant kernel's table (dial_set_plant_disturbance)
 DIM_NAMES = ("nq", "nv", "nu", "nbody", "njnt", "ngeom", "nsite", "ncon", "nlim", "nfri")
 _DIM_MACROS = ("NQ", "NV", "NU", "NB", "NJ", "NG", "NS", "NC", "NL", "NFRI")
 
@@ -116,17 +119,21 @@ def plugin_key(model, reward_src: str, flags: Sequence[str], control_src: Option
 
 
 def build_plugin(model, reward_src: str, flags: Optional[Sequence[str]] = None, verbose: bool = False,
-                 control_src: Optional[str] = None, plant: bool = False) -> str:
+                 control_src: Optional[str] = None, plant: bool = False, plant_disturbance: bool = False) -> str:
     """Compile (or find in the cache) the task plugin of `model` with the reward `reward_src` (HIP source text, or the path of a
     .hip file) and, optionally, the control law `control_src` (the same two forms) -> path of the shared library.  plant=True:
     the plugin also carries the plant simulator's kernel (-DDIAL_PLUGIN_PLANT=1; the define is one of the flags the cache key
-    hashes, so it is another library than the plugin without it).  A compile error in either source raises DialHipError with
+    hashes, so it is another library than the plugin without it).  plant_disturbance=True implies plant=True and adds the disturbed
+    plant kernel (-DDIAL_PLUGIN_PLANT_DIST=1 after it: csrc/plant_dist_kernel.h, one kernel and one symbol more, again another library;
+    the plugins built with plant=True or with neither keep their flags and keys).  A compile error in either source raises DialHipError with
     hipcc's own message."""
     import fcntl
     check_model(model)
     flags = list(_COMMON + _FAST if flags is None else flags)
-    if plant:
+    if plant or plant_disturbance:
         flags.append("-DDIAL_PLUGIN_PLANT=1")
+    if plant_disturbance:
+        flags.append("-DDIAL_PLUGIN_PLANT_DIST=1")
     reward = _read_reward(reward_src)
     control = None if control_src is None else _read_reward(control_src)
     key = plugin_key(model, reward, flags, control)[:24]

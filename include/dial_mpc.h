@@ -69,6 +69,10 @@ extern "C" {
 #define DIAL_PLANT_PD 2          /* the control row is a joint target: ctrl = clip(kp (q* - q) - kd qd, tau_range) per step */
 #define DIAL_PLANT_HOLD_FIRST 4  /* every step applies row 0 (sync mode); otherwise the row follows the clock               */
 #define DIAL_PLANT_LAW 8         /* the control row is a normalised action: ctrl = the task plugin's user control law per step */
+/* dial_set_plant_disturbance: event slots of one plant's disturbance row, and the floats of a row
+ * gain[nu] | bias[nu] | E x { t0, t1, dv[nv] } */
+#define DIAL_PLANT_MAX_EVENTS 16
+#define DIAL_PLANT_DIST_ROW(nu, nv, E) (2 * (nu) + (E) * (2 + (nv)))
 
 /* joint types (MuJoCo numbering) */
 #define DIAL_JNT_FREE 0
@@ -616,6 +620,31 @@ int dial_set_user_table(dial_ctx* ctx, const float* table, int rows, int cols, i
  * built without a plant, when libdialplant.so is missing, and in the IEEE measurement build. */
 int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_time, const float* ctrl, int T, double ctrl_dt,
                     double sim_dt, int K, int flags, float* trace, int M, void* stream);
+/* Plant disturbances: velocity kicks and actuator errors, per plant.  dist:[M, DIAL_PLANT_DIST_ROW(nu, nv, n_events)] contiguous
+ * float32 DEVICE memory, caller-owned and BOUND, not copied (the contract of dial_set_user_table: the caller keeps it alive while
+ * bound; its contents may change between launches, never during one).  Row m, of plant m:
+ *   gain[nu] | bias[nu] | n_events x { t0, t1, dv[nv] }          0 <= n_events <= DIAL_PLANT_MAX_EVENTS
+ * While a buffer is bound, dial_plant_step requires M == the bound M and runs the disturbed kernel (csrc/plant_dist_kernel.h, in
+ * libdialplantdist.so next to this library; on a task-plugin context the plugin's own, build_plugin(plant_disturbance=True), behind
+ * the optional table dial_plugin_plant_dist_v1).  Per sim step, in this order:
+ *   1. Kicks, before the control is computed (DIAL_PLANT_PD, DIAL_PLANT_LAW and the trace row see the kicked velocity): event e,
+ *      e = 0 .. n_events - 1 in index order, fires when t >= (double)t0 && t < (double)t1, t the plant's fp64 clock before the step
+ *      (the clock the row rule reads).  A firing event adds dv to qvel, one fp32 addition per dof: qvel[i] += dv[i].  An event with
+ *      t1 <= t0 (the all-zero slot) or a NaN bound never fires.  dv is in generalised velocity coordinates, in the model's units
+ *      (m/s, rad/s): behind a free base joint dofs 0-2 are the base's linear velocity in the WORLD frame, dofs 3-5 its angular
+ *      velocity in the BODY frame, the rest joint rates.  A shove that lasts d seconds is an event whose window spans d / sim_dt
+ *      steps and whose dv is the per-step increment (the host computes it: deploy/plant.py, Plant.shove).
+ *   2. Actuator error: the mode's ctrl c -- the DIAL_PLANT_CTRL row, the DIAL_PLANT_PD torque after its clip, the DIAL_PLANT_LAW
+ *      value -- becomes fma(gain[a], c, bias[a]) (one rounding).  The trace records that value; the actuators apply it like any
+ *      ctrl, their own ctrlrange clip included.
+ * gain = 1, bias = 0 and no firing event give the undisturbed plant bit for bit.  The plant's constants are still the planner's:
+ * masses, inertias, friction and geometry are NOT disturbed (that needs the model's derived constants recompiled).
+ * dist == NULL with M == 0 and n_events == 0 unbinds: dial_plant_step takes the undisturbed path again.  No synchronisation.
+ * Fails with DIAL_ERR_ARG and a message that starts with "dial_set_plant_disturbance: " on a null context, n_events outside
+ * 0 .. DIAL_PLANT_MAX_EVENTS, M < 1 or M > DIAL_MAX_PLANTS with a non-NULL buffer, a NULL buffer with M or n_events != 0;
+ * with DIAL_ERR_UNSUPPORTED when libdialplantdist.so is missing or stale, on a task plugin without the table, and in the IEEE
+ * measurement build.  dial_plant_step fails with DIAL_ERR_ARG when its M differs from the bound M. */
+int dial_set_plant_disturbance(dial_ctx* ctx, const float* dist, int M, int n_events);
 
 /* ABI self-description used by tests: sizeof of the three structs. */
 int dial_abi_sizes(int* model_bytes, int* task_bytes, int* cfg_bytes);
