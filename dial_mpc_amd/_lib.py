@@ -74,6 +74,7 @@ def build(force: bool = False, verbose: bool = False, ieee: bool = False) -> str
     if not ieee:   # the plant simulator's kernels: a library of their own next to the product library (build_plant)
         build_plant(force=force, verbose=verbose)
         build_plant_dist(force=force, verbose=verbose)
+        build_plant_var(force=force, verbose=verbose)
     return _build_lib(IEEE_LIB_PATH if ieee else LIB_PATH, [(os.path.join(_CSRC, "dial_hip.hip"), [], "dial_hip.o")] +
                       [(os.path.join(_CSRC, "kern_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []), f"kern_family_{k}.o")
                        for k in range(N_FAMILIES)], force, verbose, ieee)
@@ -101,6 +102,18 @@ def build_plant_dist(force: bool = False, verbose: bool = False) -> str:
     its own directory the first time a launch has a disturbance bound."""
     return _build_lib(PLANT_DIST_LIB_PATH, [(os.path.join(_CSRC, "plant_dist_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []),
                                              f"plant_dist_family_{k}.o") for k in range(N_PLANT_FAMILIES)], force, verbose, False)
+
+
+PLANT_VAR_LIB_PATH = os.path.join(_CSRC, "libdialplantvar.so")
+
+
+def build_plant_var(force: bool = False, verbose: bool = False) -> str:
+    """libdialplantvar.so: the plant kernel with per-plant model constants (csrc/plant_var_kernel.h: dial_set_plant_models) once per
+    robot family (plant_var_family.hip -DDIAL_FAMILY=k, build_plant's flags), a library of its own so that the code objects of
+    libdialplant.so, libdialplantdist.so and libdialhip.so stay as shipped.  libdialhip.so loads it from its own directory the first
+    time plant models are bound."""
+    return _build_lib(PLANT_VAR_LIB_PATH, [(os.path.join(_CSRC, "plant_var_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []),
+                                            f"plant_var_family_{k}.o") for k in range(N_PLANT_FAMILIES)], force, verbose, False)
 
 
 def _build_lib(out: str, units, force: bool, verbose: bool, ieee: bool) -> str:
@@ -233,6 +246,11 @@ def load(path: Optional[str] = None):
     except AttributeError:
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack plant disturbances)
             raise
+    try:
+        lib.dial_set_plant_models.argtypes = [vp, vp, ci, vp, ci]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack per-plant models)
+            raise
     lib.dial_env_reset.argtypes = [vp, fp, fp, fp, fp, fp, vp]
     lib.dial_env_reset_batch.argtypes = [vp, fp, fp, fp, fp, fp, ci, vp]
     lib.dial_status.argtypes = [vp]
@@ -260,7 +278,7 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
             "dial_status", "dial_set_timing", "dial_get_rollout_ms", "dial_abi_sizes",
             "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch",
             "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params", "dial_plant_step", "dial_user_control",
-            "dial_set_user_table", "dial_set_plant_disturbance")
+            "dial_set_user_table", "dial_set_plant_disturbance", "dial_set_plant_models")
 
 # dial_plant_step flags (include/dial_mpc.h)
 PLANT_CTRL, PLANT_PD, PLANT_HOLD_FIRST = (_abi.MACROS[k] for k in ("DIAL_PLANT_CTRL", "DIAL_PLANT_PD", "DIAL_PLANT_HOLD_FIRST"))
@@ -271,6 +289,29 @@ PLANT_MAX_EVENTS = _abi.MACROS["DIAL_PLANT_MAX_EVENTS"]   # event slots of a pla
 def plant_dist_row(nu: int, nv: int, n_events: int) -> int:
     """Floats of one plant's disturbance row, gain[nu] | bias[nu] | E x { t0, t1, dv[nv] } (DIAL_PLANT_DIST_ROW of include/dial_mpc.h)."""
     return 2 * int(nu) + int(n_events) * (2 + int(nv))
+
+
+MAX_PLANT_MODELS = _abi.MACROS["DIAL_MAX_PLANT_MODELS"]   # distinct plant models of one binding (dial_set_plant_models)
+MAX_PLANTS = _abi.MACROS["DIAL_MAX_PLANTS"]
+
+
+def plant_model_index(model_of, V: int, M: Optional[int] = None) -> np.ndarray:
+    """The index dial_set_plant_models takes: contiguous int32 [M] with 0 <= model_of[b] < V.  model_of None: M must be V (or None),
+    and plant b runs model b.  Raises ValueError on another shape, a non-integer or an index out of range."""
+    V = int(V)
+    if not 1 <= V <= MAX_PLANT_MODELS:
+        raise ValueError(f"plant models: {V} models; 1 .. DIAL_MAX_PLANT_MODELS = {MAX_PLANT_MODELS} are allowed")
+    if model_of is None:
+        if M is not None and int(M) != V:
+            raise ValueError(f"plant models: {V} models for M = {M} plants need a model_of (without one, plant b runs model b)")
+        return np.arange(V, dtype=np.int32)
+    a = np.asarray(model_of)
+    if a.ndim != 1 or a.size < 1 or a.size > MAX_PLANTS or not np.issubdtype(a.dtype, np.integer) or (M is not None and a.size != int(M)):
+        raise ValueError(f"plant models: model_of is an integer list of one index per plant{'' if M is None else f' (M = {M})'}; got "
+                         f"shape {a.shape}, dtype {a.dtype}")
+    if a.min() < 0 or a.max() >= V:
+        raise ValueError(f"plant models: model_of holds indices outside 0 .. V - 1 = {V - 1}")
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def plan_param_rows(rows) -> np.ndarray:
@@ -558,6 +599,24 @@ class Context:
         self._check(self.lib.dial_set_plant_disturbance(self.h, _ptr(dist), int(dist.shape[0]), n_events), "dial_set_plant_disturbance")
         self._plant_dist = dist
         return dist
+
+    def set_plant_models(self, models, model_of=None):
+        """Bind per-plant model constants (dial_set_plant_models): `models` a list of V compiled model dicts or DialModel structs --
+        variants of this context's model with the same structure and timestep (mjcf.vary_model makes them) --, `model_of` an integer
+        list [M], plant b runs models[model_of[b]] (None: V == M, one to one).  The library copies both.  While bound, plant_step
+        needs M == len(model_of) and runs the per-plant-model kernel.  models None unbinds."""
+        if models is None:
+            self._check(self.lib.dial_set_plant_models(self.h, None, 0, None, 0), "dial_set_plant_models")
+            return None
+        models = list(models)
+        index = plant_model_index(model_of, len(models))
+        arr = (_abi.DialModel * len(models))()
+        for v, m in enumerate(models):
+            struct = m if isinstance(m, _abi.DialModel) else _abi.make_model(m)   # (kept alive across the copy)
+            ctypes.memmove(ctypes.addressof(arr[v]), ctypes.addressof(struct), ctypes.sizeof(_abi.DialModel))
+        self._check(self.lib.dial_set_plant_models(self.h, ctypes.addressof(arr), len(models), index.ctypes.data, int(index.size)),
+                    "dial_set_plant_models")
+        return index
 
     # ---- K3
     def rollout(self, state, us, want_states: bool = True):

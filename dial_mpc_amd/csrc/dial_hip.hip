@@ -25,6 +25,7 @@
 #include "plant_kernel.h"
 #include "plant_plugin.h"
 #include "plant_dist_kernel.h"
+#include "plant_var_kernel.h"
 #include "plugin_ops.h"
 
 // the kernels are compiled in their own translation units, one per robot family (kern_family.hip, built in parallel)
@@ -356,6 +357,13 @@ struct dial_ctx {
   const dial_plugin_plant_dist* plug_plant_dist = nullptr;   // inst 7: the plugin's disturbed plant kernel, nullptr: built without one
   const float* plant_dist = nullptr;       // plant disturbances (dial_set_plant_disturbance), caller-owned device rows ...
   int plant_dist_M = 0, plant_dist_E = 0;  // ... [plant_dist_M, DIAL_PLANT_DIST_ROW(nu, nv, plant_dist_E)]; nullptr: the undisturbed plant
+  const dial_plugin_plant_var* plug_plant_var = nullptr;     // inst 7: the plugin's per-plant-model plant kernel, nullptr: built without one
+  void* plant_models = nullptr;            // per-plant model constants (dial_set_plant_models), context-owned: V blocks of constants,
+  int32_t* plant_model_of = nullptr;       // (sizeof(CModel<D>) + 15) / 16 * 16 bytes apart, and the index int32[M]; nullptr: the context's own model
+  int plant_models_V = 0, plant_models_M = 0;
+  std::vector<float> user_params;          // inst 7: the current user parameters and reference-table binding, as dial_create_plugin /
+  const float* user_table = nullptr;       // dial_set_user_params / dial_set_user_table last set them (dial_set_plant_models writes
+  int user_table_rows = 0, user_table_cols = 0, user_table_row0 = 0, user_table_mode = 0;   // them into every block it builds)
   std::vector<char> plug_cm;               // inst 7: host copy of the constants (dial_set_user_params rewrites the parameters)
   const float* plan_params = nullptr;      // inst 7: per-plan task parameters (dial_set_plan_params), caller-owned device rows ...
   int plan_rows = 0;                       // ... [plan_rows, DIAL_USER_PARAMS]; nullptr: every launch reads the shared ones
@@ -446,6 +454,15 @@ static int plugin_table(void* h, const char* plugin_path, const char* symbol, co
   return DIAL_OK;
 }
 
+// dial_set_plant_models: one block of constants of a built-in instantiation, as dial_create's upload builds it
+template <class D>
+static void plant_model_block(void* dst, const dial_model* model, const dial_task* task, const dial_derived* dv) {
+  CModel<D>* h = new CModel<D>();
+  fill_cmodel(h, model, task, dv);
+  memcpy(dst, h, sizeof(CModel<D>));
+  delete h;
+}
+
 extern "C" {
 
 const char* dial_last_error(const dial_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
@@ -461,7 +478,8 @@ void dial_destroy(dial_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   void* ptrs[] = {ctx->dcm, ctx->dtask, ctx->dcfg, ctx->prof, ctx->next, ctx->relay_buf, ctx->relay_flag, ctx->Y0s, ctx->rewss, ctx->rews, ctx->qss,
-                  ctx->qdss,   ctx->xss,   ctx->weights, ctx->partial, ctx->ovf, ctx->slice_buf, ctx->slice_flag, ctx->work_stat};
+                  ctx->qdss,   ctx->xss,   ctx->weights, ctx->partial, ctx->ovf, ctx->slice_buf, ctx->slice_flag, ctx->work_stat,
+                  ctx->plant_models, ctx->plant_model_of};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -538,8 +556,13 @@ int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task*
   if (int rc = plugin_table(h, plugin_path, DIAL_PLUGIN_PLANT_DIST_SYMBOL, "plant-disturbance table", DIAL_PLUGIN_PLANT_DIST_VERSION, &pld)) return rc;
   if (pld && (!pla || pld->cmodel_bytes != ops->cmodel_bytes || pld->nq != model->nq || pld->nv != model->nv || pld->nu != model->nu || !pld->launch))
     return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's plant-disturbance table was built against another version of the library (ABI mismatch; rebuild it)");
+  // the per-plant-model plant kernel's table: a sixth symbol, exported only by a plugin built with build_plugin(plant_models=True)
+  const dial_plugin_plant_var* plv;
+  if (int rc = plugin_table(h, plugin_path, DIAL_PLUGIN_PLANT_VAR_SYMBOL, "plant-models table", DIAL_PLUGIN_PLANT_VAR_VERSION, &plv)) return rc;
+  if (plv && (!pla || plv->cmodel_bytes != ops->cmodel_bytes || plv->nq != model->nq || plv->nv != model->nv || plv->nu != model->nu || !plv->launch))
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's plant-models table was built against another version of the library (ABI mismatch; rebuild it)");
   const int rc = create_impl(out, model, task, cfg, device, -1, opts, ops, params, n_params);
-  if (rc == DIAL_OK) { (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; (*out)->plug_plant = pla; (*out)->plug_plant_dist = pld; }
+  if (rc == DIAL_OK) { (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; (*out)->plug_plant = pla; (*out)->plug_plant_dist = pld; (*out)->plug_plant_var = plv; }
   return rc;
 }
 
@@ -560,8 +583,12 @@ int dial_user_control(dial_ctx* ctx, const float* states, const float* actions, 
 int dial_set_user_params(dial_ctx* ctx, const float* params, int n) {
   if (!ctx || n < 0 || n > DIAL_USER_PARAMS || (n > 0 && !params)) return fail(ctx, DIAL_ERR_ARG, "dial_set_user_params: bad argument (n must be in 0 .. DIAL_USER_PARAMS)");
   if (!ctx->plug) return fail(ctx, DIAL_ERR_ARG, "dial_set_user_params: the context has no task plugin (dial_create_plugin)");
+  if (ctx->plant_models)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_user_params: plant models are bound, and their constants carry a copy of the parameters; unbind first "
+                                   "(dial_set_plant_models(ctx, NULL, 0, NULL, 0)), then bind again");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->plug->set_params(ctx->plug_cm.data(), params, n);
+  ctx->user_params.assign(params, params + n);
   HIP_TRY(ctx, hipDeviceSynchronize());   // (launches in flight read the constants)
   HIP_TRY(ctx, hipMemcpy(ctx->dcm, ctx->plug_cm.data(), ctx->plug->cmodel_bytes, hipMemcpyHostToDevice));
   return DIAL_OK;
@@ -580,8 +607,12 @@ int dial_set_user_table(dial_ctx* ctx, const float* table, int rows, int cols, i
   if (!ctx->plug_table)
     return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_set_user_table: the context's task plugin does not export " DIAL_PLUGIN_TABLE_SYMBOL
                                            " (built before the reference table existed; rebuild it)");
+  if (ctx->plant_models)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_user_table: plant models are bound, and their constants carry a copy of the table's binding; unbind first "
+                                   "(dial_set_plant_models(ctx, NULL, 0, NULL, 0)), then bind again");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->plug_table->set_table(ctx->plug_cm.data(), table, rows, cols, row0, mode);
+  ctx->user_table = table; ctx->user_table_rows = rows; ctx->user_table_cols = cols; ctx->user_table_row0 = row0; ctx->user_table_mode = mode;
   HIP_TRY(ctx, hipDeviceSynchronize());   // (launches in flight read the constants)
   HIP_TRY(ctx, hipMemcpy(ctx->dcm, ctx->plug_cm.data(), ctx->plug->cmodel_bytes, hipMemcpyHostToDevice));
   return DIAL_OK;
@@ -607,6 +638,28 @@ static int check_plan_rows(dial_ctx* ctx, int M, const char* who) {
     return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": M = " + std::to_string(M) + " exceeds the " + std::to_string(ctx->plan_rows) +
                                    " rows of per-plan task parameters bound with dial_set_plan_params");
   return DIAL_OK;
+}
+
+// The built-in kernel instantiation dial_create picks for a model (dial_ctx::inst 0 .. 6), given the task, the derived constants and the
+// options; -1: an elliptic-cone model that no dimension-specialised instantiation serves (dial_create fails).  dial_set_plant_models
+// accepts a plant model only when this picks the context's instantiation for it.
+static int select_inst(const dial_model* model, const dial_task* task, const dial_derived* hd, const dial_options& opt) {
+  const auto kind_ok = [&](uint32_t mask) { return ((mask >> task->kind) & 1u) != 0; };   // the robot's own task kinds only
+  // the robot's own dimension-specialised instantiation (default) -- unless the model has more distinct (solref, solimp) rows than
+  // their impedance table holds (CModel::kbi_tab; the shipped robots have two or three)
+  const bool kbi_ok = kbi_unique_rows(model) <= DIAL_KBI_ROWS;
+  const bool own = !opt.force_generic && kbi_ok;
+  // (Dims::pre_ctrl instantiations run ONE physics step per control step -- every shipped Go2 task; another ratio: the capacity-dimension kernel)
+  if (own && dims_match<DimsGo2>(model) && derived_fits<DimsGo2>(hd) && kind_ok(dial::task_kind_mask<DimsGo2>()) &&
+      (!DimsGo2::pre_ctrl || task->n_frames == 1)) return 1;
+  if (own && dims_match<DimsH1>(model) && derived_fits<DimsH1>(hd) && kind_ok(dial::task_kind_mask<DimsH1>())) return 2;
+  if (own && dims_match<DimsH1Loco>(model) && derived_fits<DimsH1Loco>(hd) && kind_ok(dial::task_kind_mask<DimsH1Loco>())) return 3;
+  if (model->cone == DIAL_CONE_ELLIPTIC)   // (options.force_generic included: the capacity-dimension kernel has no elliptic-cone solver)
+    return (opt.force_generic || !(kbi_ok && dims_match<DimsAllegro>(model) && ell_fits<DimsAllegro>(model, hd))) ? -1 : 4;
+  // (options.con_cap < 0 -- no cap, the full-size workspace -- does not fit nine wavefronts per workgroup: capacity-dimension kernel)
+  if (own && opt.con_cap >= 0 && dims_match<DimsGo2Crate>(model) && kind_ok(dial::task_kind_mask<DimsGo2Crate>())) return 5;
+  if (own && opt.con_cap >= 0 && dims_match<DimsH1PushCrate>(model) && kind_ok(dial::task_kind_mask<DimsH1PushCrate>())) return 6;
+  return 0;
 }
 
 static int create_impl(dial_ctx** out, const dial_model* model, const dial_task* task, const dial_cfg* cfg, int device,
@@ -760,12 +813,6 @@ static int create_impl(dial_ctx** out, const dial_model* model, const dial_task*
       return e == hipSuccess ? DIAL_OK : DIAL_ERR_HIP;
     };
     int urc;
-    const auto kind_ok = [&](uint32_t mask) { return ((mask >> task->kind) & 1u) != 0; };   // the robot's own task kinds only
-    // the robot's own dimension-specialised instantiation (default) -- unless the model has more distinct (solref, solimp) rows than
-    // their impedance table holds (CModel::kbi_tab; the shipped robots have two or three)
-    const bool kbi_ok = kbi_unique_rows(model) <= DIAL_KBI_ROWS;
-    const bool own = !opt.force_generic && kbi_ok;
-    // (Dims::pre_ctrl instantiations run ONE physics step per control step -- every shipped Go2 task; another ratio: the capacity-dimension kernel)
     if (plug) {   // a task plugin: its own instantiation, whatever the options say about the built-in ones
       ctx->inst = 7; ctx->wpb = plug->wpb;
       if (const char* why = plug->check(model, &ctx->hd)) { dial_destroy(ctx); return fail(nullptr, DIAL_ERR_ARG, std::string("dial_create_plugin: ") + why); }
@@ -779,28 +826,25 @@ static int create_impl(dial_ctx** out, const dial_model* model, const dial_task*
       ctx->lds_rollout = ctx->cm_bytes + (size_t)ctx->wpb * ctx->ws_words * sizeof(float);
       ctx->plug_cm.assign(plug->cmodel_bytes, 0);
       plug->fill(ctx->plug_cm.data(), model, task, &ctx->hd, params, n_params);
+      if (params && n_params > 0) ctx->user_params.assign(params, params + n_params);
       ctx->dcm_bytes = plug->cmodel_bytes;
       hipError_t e = hipMalloc(&ctx->dcm, (plug->cmodel_bytes + 15) / 16 * 16);
       if (e == hipSuccess) e = hipMemcpy(ctx->dcm, ctx->plug_cm.data(), plug->cmodel_bytes, hipMemcpyHostToDevice);
       urc = e == hipSuccess ? DIAL_OK : DIAL_ERR_HIP;
     }
-    else if (own && dims_match<DimsGo2>(model) && derived_fits<DimsGo2>(&ctx->hd) && kind_ok(dial::task_kind_mask<DimsGo2>()) &&
-        (!DimsGo2::pre_ctrl || task->n_frames == 1)) { ctx->inst = 1; ctx->wpb = 1; urc = upload(DimsGo2{}); }
-    else if (own && dims_match<DimsH1>(model) && derived_fits<DimsH1>(&ctx->hd) && kind_ok(dial::task_kind_mask<DimsH1>())) { ctx->inst = 2; ctx->wpb = 3; urc = upload(DimsH1{}); }
-    else if (own && dims_match<DimsH1Loco>(model) && derived_fits<DimsH1Loco>(&ctx->hd) && kind_ok(dial::task_kind_mask<DimsH1Loco>())) { ctx->inst = 3; ctx->wpb = 2; urc = upload(DimsH1Loco{}); }
-    else if (model->cone == DIAL_CONE_ELLIPTIC) {
-      // (options.force_generic included: the capacity-dimension kernel has no elliptic-cone solver)
-      if (opt.force_generic || !(kbi_ok && dims_match<DimsAllegro>(model) && ell_fits<DimsAllegro>(model, &ctx->hd))) {
+    else switch (select_inst(model, task, &ctx->hd, opt)) {   // (the selection: select_inst, shared with dial_set_plant_models)
+      case 1: ctx->inst = 1; ctx->wpb = 1; urc = upload(DimsGo2{}); break;
+      case 2: ctx->inst = 2; ctx->wpb = 3; urc = upload(DimsH1{}); break;
+      case 3: ctx->inst = 3; ctx->wpb = 2; urc = upload(DimsH1Loco{}); break;
+      case 4: ctx->inst = 4; ctx->wpb = DIAL_ALLEGRO_WPB; urc = upload(DimsAllegro{}); break;
+      case 5: ctx->inst = 5; ctx->wpb = DIAL_CRATE_WPB; urc = upload(DimsGo2Crate{}); break;
+      case 6: ctx->inst = 6; ctx->wpb = DIAL_CRATE_WPB; urc = upload(DimsH1PushCrate{}); break;
+      case 0: ctx->inst = 0; ctx->wpb = 1; urc = upload(DimsMax{}); break;
+      default:
         dial_destroy(ctx);
         return fail(nullptr, DIAL_ERR_UNSUPPORTED, std::string("dial_create: elliptic-cone models need a dimension-specialised instantiation (built: Allegro hand)") +
                                                    (opt.force_generic ? "; options.force_generic does not apply to them" : ""));
-      }
-      ctx->inst = 4; ctx->wpb = DIAL_ALLEGRO_WPB; urc = upload(DimsAllegro{});
     }
-    // (options.con_cap < 0 -- no cap, the full-size workspace -- does not fit nine wavefronts per workgroup: capacity-dimension kernel)
-    else if (own && opt.con_cap >= 0 && dims_match<DimsGo2Crate>(model) && kind_ok(dial::task_kind_mask<DimsGo2Crate>())) { ctx->inst = 5; ctx->wpb = DIAL_CRATE_WPB; urc = upload(DimsGo2Crate{}); }
-    else if (own && opt.con_cap >= 0 && dims_match<DimsH1PushCrate>(model) && kind_ok(dial::task_kind_mask<DimsH1PushCrate>())) { ctx->inst = 6; ctx->wpb = DIAL_CRATE_WPB; urc = upload(DimsH1PushCrate{}); }
-    else { ctx->inst = 0; ctx->wpb = 1; urc = upload(DimsMax{}); }
     if (urc != DIAL_OK) { dial_destroy(ctx); return fail(nullptr, urc, "dial_create: uploading the model constants failed"); }
     ctx->last_launch[LF_INST] = ctx->inst;   // (dial_debug_last_launch before any rollout launch: the instantiation, blocks = 0)
   }
@@ -1674,6 +1718,183 @@ int dial_set_plant_disturbance(dial_ctx* ctx, const float* dist, int M, int n_ev
   return DIAL_OK;
 }
 
+#ifndef DIAL_IEEE_BUILD
+// libdialplantvar.so (plant_var_family.hip): the plant kernels with per-plant model constants, looked up the first time models are bound
+struct PlantVarLib {
+  const dial_plant_var_ops* ops = nullptr;
+  std::string err;
+};
+static PlantVarLib plant_var_load() {
+  PlantVarLib r;
+  Dl_info info{};
+  std::string dir = ".";
+  if (dladdr((const void*)&plant_var_load, &info) && info.dli_fname) {
+    dir = info.dli_fname;
+    const size_t slash = dir.rfind('/');
+    dir = slash == std::string::npos ? "." : dir.substr(0, slash);
+  }
+  const std::string path = dir + "/libdialplantvar.so";
+  void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);   // (never dlclose'd: the runtime holds its code objects)
+  if (!h) { r.err = "cannot load " + path + " (build it: dial_mpc_amd._lib.build()): " + dlerror(); return r; }
+  dial_plant_var_entry entry = (dial_plant_var_entry)dlsym(h, DIAL_PLANT_VAR_SYMBOL);
+  const dial_plant_var_ops* o = entry ? entry() : nullptr;
+  if (!o) r.err = path + " does not export " DIAL_PLANT_VAR_SYMBOL;
+  else if (o->abi_version != DIAL_PLANT_VAR_ABI_VERSION || o->sizeof_model != sizeof(dial_model) || o->sizeof_task != sizeof(dial_task))
+    r.err = path + " was built against another version of the library (rebuild it)";
+  else r.ops = o;
+  return r;
+}
+static const PlantVarLib& plant_var_lib() {
+  static const PlantVarLib lib = plant_var_load();   // (once per process, thread-safe initialisation)
+  return lib;
+}
+#endif
+
+// The per-plant-model kernel's launch function of a context: the plugin's sixth table, or libdialplantvar.so's entry of the context's
+// instantiation.  nullptr with the reason in `why` (DIAL_ERR_UNSUPPORTED).
+static dial_plant_var_launch_fn plant_var_launch_of(dial_ctx* ctx, std::string& why) {
+#ifdef DIAL_IEEE_BUILD
+  (void)ctx;
+  why = "the IEEE measurement build carries no plant (use the product library)";
+  return nullptr;
+#else
+  if (ctx->plug) {
+    if (!ctx->plug_plant_var) {
+      why = "the context's task plugin does not export " DIAL_PLUGIN_PLANT_VAR_SYMBOL " (build it with build_plugin(plant_models=True); "
+            "CustomEnv.make_plant(models=True) does)";
+      return nullptr;
+    }
+    return ctx->plug_plant_var->launch;
+  }
+  const PlantVarLib& lib = plant_var_lib();
+  if (!lib.ops) { why = lib.err; return nullptr; }
+  if (ctx->inst < 0 || ctx->inst >= DIAL_PLANT_INSTS || lib.ops->cmodel_bytes[ctx->inst] != ctx->dcm_bytes) {
+    why = "libdialplantvar.so does not match this library's constants (rebuild both)";
+    return nullptr;
+  }
+  if (!lib.ops->launch[ctx->inst]) {
+    why = "libdialplantvar.so carries no per-plant-model kernel for kernel instantiation " + std::to_string(ctx->inst);
+    return nullptr;
+  }
+  return lib.ops->launch[ctx->inst];
+#endif
+}
+
+#ifndef DIAL_IEEE_BUILD
+// dial_set_plant_models: why the context cannot run `model` as one of its plants (empty: it can), and its derived constants in *dv.
+static std::string plant_model_refusal(const dial_ctx* ctx, const dial_model* model, dial_derived* dv) {
+  const dial_model& hm = ctx->hm;
+  // the dimensions size the LDS workspace of the launch and the strides of states, rows and traces: the context's, all of them
+  const int mine[11] = {hm.nq, hm.nv, hm.nu, hm.nbody, hm.njnt, hm.ngeom, hm.nsite, hm.ncon, hm.nlim, hm.nfri, hm.nefc};
+  const int its[11] = {model->nq, model->nv, model->nu, model->nbody, model->njnt, model->ngeom, model->nsite, model->ncon, model->nlim, model->nfri, model->nefc};
+  static const char* const names[11] = {"nq", "nv", "nu", "nbody", "njnt", "ngeom", "nsite", "ncon", "nlim", "nfri", "nefc"};
+  for (int k = 0; k < 11; k++)
+    if (mine[k] != its[k])
+      return std::string(names[k]) + " = " + std::to_string(its[k]) + ", the context's model has " + std::to_string(mine[k]) + " (a plant model varies constants, not the structure)";
+  if (model->cone != hm.cone || model->ls_rule != hm.ls_rule || model->eulerdamp != hm.eulerdamp)
+    return "its cone, line-search rule or eulerdamp differs from the context's model";
+  for (int c = 0; c < hm.ncon; c++) {
+    if (model->con_kind[c] != hm.con_kind[c] || model->con_dim[c] != hm.con_dim[c]) return "the kind or dimension of contact " + std::to_string(c) + " differs from the context's model";
+    if (model->con_kind[c] >= DIAL_CON_PLANE_BOX && !(model->con_margin[c] < DIAL_BOX_PARK_DIST)) return "box contacts need margin < 0.01 m";
+  }
+  if (dial_build_derived(model, dv) != DIAL_OK) return "unsupported model topology (dial_build_derived fails)";
+  if (ctx->plug) {
+    if (model->cone != DIAL_CONE_PYRAMIDAL) return "task plugins support pyramidal friction cones only";
+    if (kbi_unique_rows(model) > DIAL_KBI_ROWS) return "it has more distinct (solref, solimp) rows than the impedance table holds (DIAL_KBI_ROWS)";
+    if (const char* why = ctx->plug->check(model, dv)) return why;
+  } else {
+    const int inst = select_inst(model, &ctx->ht, dv, ctx->opt);
+    if (inst != ctx->inst)
+      return "dial_create would pick kernel instantiation " + std::to_string(inst) + " for it, the context runs instantiation " + std::to_string(ctx->inst) +
+             " (another dof tree or contact layout, or more distinct (solref, solimp) rows than DIAL_KBI_ROWS)";
+  }
+  if (model->timestep != hm.timestep)
+    return "its timestep " + std::to_string(model->timestep) + " differs from the context's " + std::to_string(hm.timestep);
+  bool same = model->jnt_type[0] == hm.jnt_type[0] && model->jnt_qposadr[0] == hm.jnt_qposadr[0];
+  for (int a = 0; a < hm.nu && same; a++)
+    same = model->act_isposition[a] == hm.act_isposition[a] && model->act_qposadr[a] == hm.act_qposadr[a] && model->act_dofadr[a] == hm.act_dofadr[a];
+  if (!same) return "its actuators or first joint (act_isposition, act_qposadr, act_dofadr, jnt_type[0], jnt_qposadr[0]) differ from the context's model";
+  return std::string();
+}
+
+#endif
+
+int dial_set_plant_models(dial_ctx* ctx, const dial_model* models, int V, const int32_t* model_of, int M) {
+  if (!ctx) return fail(nullptr, DIAL_ERR_ARG, "dial_set_plant_models: null context");
+  if (!models && !model_of && V == 0 && M == 0) {   // unbind
+    if (ctx->plant_models) {
+      HIP_TRY(ctx, hipSetDevice(ctx->device));
+      HIP_TRY(ctx, hipDeviceSynchronize());   // (launches in flight read the blocks)
+      (void)hipFree(ctx->plant_models);
+      (void)hipFree(ctx->plant_model_of);
+    }
+    ctx->plant_models = nullptr;
+    ctx->plant_model_of = nullptr;
+    ctx->plant_models_V = ctx->plant_models_M = 0;
+    return DIAL_OK;
+  }
+  if (V < 1 || V > DIAL_MAX_PLANT_MODELS)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plant_models: V = " + std::to_string(V) + " is outside 1 .. DIAL_MAX_PLANT_MODELS");
+  if (M < 1 || M > DIAL_MAX_PLANTS)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plant_models: M = " + std::to_string(M) + " is outside 1 .. DIAL_MAX_PLANTS");
+  if (!models || !model_of)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plant_models: a null pointer with V = " + std::to_string(V) + ", M = " + std::to_string(M) +
+                                   " (NULL, 0, NULL, 0 unbinds)");
+  for (int b = 0; b < M; b++)
+    if (model_of[b] < 0 || model_of[b] >= V)
+      return fail(ctx, DIAL_ERR_ARG, "dial_set_plant_models: model_of[" + std::to_string(b) + "] = " + std::to_string(model_of[b]) + " is outside 0 .. V - 1 = " +
+                                     std::to_string(V - 1));
+  std::string why;
+  if (!plant_var_launch_of(ctx, why)) return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_set_plant_models: " + why);
+#ifndef DIAL_IEEE_BUILD
+  // the V blocks on the host: what dial_create uploads for each model, `stride` bytes apart (the kernels stage 16-byte words)
+  const size_t stride = (ctx->dcm_bytes + 15) / 16 * 16;
+  std::vector<char> blocks((size_t)V * stride, 0);
+  std::vector<dial_derived> dvs(1);
+  for (int v = 0; v < V; v++) {
+    const dial_model* mv = models + v;
+    const std::string no = plant_model_refusal(ctx, mv, &dvs[0]);
+    if (!no.empty()) return fail(ctx, DIAL_ERR_ARG, "dial_set_plant_models: model " + std::to_string(v) + " is rejected: " + no);
+    char* dst = blocks.data() + (size_t)v * stride;
+    if (ctx->plug) {   // the context's current parameters and reference table, through the functions that wrote them into plug_cm
+      ctx->plug->fill(dst, mv, &ctx->ht, &dvs[0], ctx->user_params.data(), (int)ctx->user_params.size());
+      if (ctx->plug_table && ctx->user_table)
+        ctx->plug_table->set_table(dst, ctx->user_table, ctx->user_table_rows, ctx->user_table_cols, ctx->user_table_row0, ctx->user_table_mode);
+    } else {
+      switch (ctx->inst) {
+        case 0: plant_model_block<DimsMax>(dst, mv, &ctx->ht, &dvs[0]); break;
+        case 1: plant_model_block<DimsGo2>(dst, mv, &ctx->ht, &dvs[0]); break;
+        case 2: plant_model_block<DimsH1>(dst, mv, &ctx->ht, &dvs[0]); break;
+        case 3: plant_model_block<DimsH1Loco>(dst, mv, &ctx->ht, &dvs[0]); break;
+        case 4: plant_model_block<DimsAllegro>(dst, mv, &ctx->ht, &dvs[0]); break;
+        case 5: plant_model_block<DimsGo2Crate>(dst, mv, &ctx->ht, &dvs[0]); break;
+        default: plant_model_block<DimsH1PushCrate>(dst, mv, &ctx->ht, &dvs[0]); break;   // (6: plant_var_launch_of has checked the range)
+      }
+    }
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  void* dblocks = nullptr;
+  int32_t* dindex = nullptr;
+  hipError_t e = hipMalloc(&dblocks, blocks.size());
+  if (e == hipSuccess) e = hipMalloc((void**)&dindex, (size_t)M * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemcpy(dblocks, blocks.data(), blocks.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dindex, model_of, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // (launches in flight read the previous binding's blocks)
+  if (e != hipSuccess) {
+    if (dblocks) (void)hipFree(dblocks);
+    if (dindex) (void)hipFree(dindex);
+    return fail(ctx, DIAL_ERR_HIP, std::string("dial_set_plant_models: uploading the constants failed: ") + hipGetErrorString(e));
+  }
+  if (ctx->plant_models) (void)hipFree(ctx->plant_models);
+  if (ctx->plant_model_of) (void)hipFree(ctx->plant_model_of);
+  ctx->plant_models = dblocks;
+  ctx->plant_model_of = dindex;
+  ctx->plant_models_V = V;
+  ctx->plant_models_M = M;
+#endif
+  return DIAL_OK;
+}
+
 int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_time, const float* ctrl, int T, double ctrl_dt,
                     double sim_dt, int K, int flags, float* trace, int M, void* stream) {
   if (!ctx) return fail(nullptr, DIAL_ERR_ARG, "dial_plant_step: null context");
@@ -1715,10 +1936,23 @@ int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_t
   (void)trace; (void)stream;
   return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: the IEEE measurement build carries no plant (use the product library)");
 #else
-  if (ctx->plant_dist) {   // a disturbance is bound (dial_set_plant_disturbance): the disturbed kernel, one row of the buffer per plant
-    if (M != ctx->plant_dist_M)
-      return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: M = " + std::to_string(M) + ", but the bound plant disturbance has " + std::to_string(ctx->plant_dist_M) +
-                                     " rows (dial_set_plant_disturbance)");
+  if (ctx->plant_dist && M != ctx->plant_dist_M)   // a disturbance is bound (dial_set_plant_disturbance): one row of the buffer per plant
+    return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: M = " + std::to_string(M) + ", but the bound plant disturbance has " + std::to_string(ctx->plant_dist_M) +
+                                   " rows (dial_set_plant_disturbance)");
+  if (ctx->plant_models) {   // plant models are bound (dial_set_plant_models): plant b stages block model_of[b]; the disturbance, if any, rides along
+    if (M != ctx->plant_models_M)
+      return fail(ctx, DIAL_ERR_ARG, "dial_plant_step: M = " + std::to_string(M) + ", but the bound plant models index " + std::to_string(ctx->plant_models_M) +
+                                     " plants (dial_set_plant_models)");
+    std::string why;
+    dial_plant_var_launch_fn vlaunch = plant_var_launch_of(ctx, why);
+    if (!vlaunch) return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: " + why);
+    if (int rc = check_sticky(ctx)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, vlaunch(ctx->plant_models, ctx->lds_bytes, (hipStream_t)stream, states, t, plan_time, ctrl, T, ctrl_dt, sim_dt, K, flags, trace, M,
+                         ctx->plant_dist, ctx->plant_dist ? ctx->plant_dist_E : 0, ctx->plant_model_of));
+    return DIAL_OK;
+  }
+  if (ctx->plant_dist) {   // the disturbed kernel
     std::string why;
     dial_plant_dist_launch_fn dlaunch = plant_dist_launch_of(ctx, why);
     if (!dlaunch) return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_plant_step: " + why);

@@ -6,6 +6,8 @@
 // __restrict__ on the body's parameters -- changes the register allocation of plant_kernel in every family (Go2 182 -> 178 VGPRs,
 // Go2 crate 136 -> 140, ...), and libdialplant.so's code objects are pinned (tests/golden/plant_kernel_resources.txt).  A change
 // to plant_kernel's loop must be made here too; tests/test_gpu_plant_dist.py compares the two bit for bit under identity data.
+// plant_var_kernel.h (per-plant model constants) restates the loop a third time, kicks and actuator errors included: a change to the
+// loop must be made in all three headers (plant_kernel.h, plant_dist_kernel.h, plant_var_kernel.h).
 // The kernel is opt-in and lives in code objects of its own:
 //   - libdialplantdist.so (plant_dist_family.hip, one translation unit per robot family), looked up by libdialhip.so through the
 //     table below (dlopen on first use) -- libdialplant.so and libdialhip.so gain no kernel;

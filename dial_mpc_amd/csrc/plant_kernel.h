@@ -16,6 +16,9 @@
 // (global memory), info_user = the state's slots as they are, params = the shared parameters, the table row of that step straight
 // from global memory (no ring: the plant has no reward that would read it after the physics).  Per step the law's control phase
 // issues two kinds of global loads, the row and the table row; everything else the law reads is LDS (the staged constants, the state).
+// The step loop below is RESTATED in plant_dist_kernel.h (velocity kicks, actuator errors) and in plant_var_kernel.h (per-plant model
+// constants), because sharing one inlined body moves this kernel's pinned register allocation: a change to the loop must be made in
+// all three headers (plant_kernel.h, plant_dist_kernel.h, plant_var_kernel.h); the GPU tests compare them bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -11,6 +11,8 @@
 // families, with the law as a third control mode) and exports a fourth, dial_plugin_plant (plant_plugin.h: dial_plant_step on the
 // plugin's contexts).  -DDIAL_PLUGIN_PLANT_DIST=1 next to it (build_plugin(plant_disturbance=True)) adds plant_dist_kernel<DimsPlugin>
 // (plant_dist_kernel.h: velocity kicks and actuator errors, dial_set_plant_disturbance) and a fifth table, dial_plugin_plant_dist.
+// -DDIAL_PLUGIN_PLANT_VAR=1 next to DIAL_PLUGIN_PLANT (build_plugin(plant_models=True)) adds plant_var_kernel<DimsPlugin>
+// (plant_var_kernel.h: per-plant model constants, dial_set_plant_models) and a sixth table, dial_plugin_plant_var.
 #include "plugin_ops.h"
 #ifndef DIAL_PLUGIN_PLANT
 #define DIAL_PLUGIN_PLANT 0
@@ -21,11 +23,20 @@
 #if DIAL_PLUGIN_PLANT_DIST && !DIAL_PLUGIN_PLANT
 #error "DIAL_PLUGIN_PLANT_DIST needs DIAL_PLUGIN_PLANT"
 #endif
+#ifndef DIAL_PLUGIN_PLANT_VAR
+#define DIAL_PLUGIN_PLANT_VAR 0
+#endif
+#if DIAL_PLUGIN_PLANT_VAR && !DIAL_PLUGIN_PLANT
+#error "DIAL_PLUGIN_PLANT_VAR needs DIAL_PLUGIN_PLANT"
+#endif
 #if DIAL_PLUGIN_PLANT
 #include "plant_plugin.h"
 #endif
 #if DIAL_PLUGIN_PLANT_DIST
 #include "plant_dist_kernel.h"
+#endif
+#if DIAL_PLUGIN_PLANT_VAR
+#include "plant_var_kernel.h"
 #endif
 #include "dial_plugin_dims.h"
 #include "dial_user_reward.hip"
@@ -86,5 +97,14 @@ template __global__ void plant_dist_kernel<DimsPlugin>(const CModel<DimsPlugin>*
 
 extern "C" __attribute__((visibility("default"))) const dial_plugin_plant_dist* dial_plugin_plant_dist_v1(void) {
   return PluginPlantDist<DimsPlugin>::table();
+}
+#endif
+
+#if DIAL_PLUGIN_PLANT_VAR
+template __global__ void plant_var_kernel<DimsPlugin>(const CModel<DimsPlugin>*, float*, double*, const float*, const float*, int, double, double,
+                                                       int, int, float*, const float*, int, const int32_t*);
+
+extern "C" __attribute__((visibility("default"))) const dial_plugin_plant_var* dial_plugin_plant_var_v1(void) {
+  return PluginPlantVar<DimsPlugin>::table();
 }
 #endif

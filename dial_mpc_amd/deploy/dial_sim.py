@@ -10,8 +10,11 @@ sim_dt / real_time_factor of wall time.  Sync mode: after each published plan, t
 (plant.sync_steps), in one launch.
 
 ``sim_disturbance`` (optional) disturbs the plant, not the planner's model: an actuator gain / bias (a weak or offset motor) and
-timed shoves of the base (deploy/plant.py: Plant.shove; csrc/plant_dist_kernel.h).  The plant's constants -- masses, inertias,
-friction, geometry -- stay the planner's.
+timed shoves of the base (deploy/plant.py: Plant.shove; csrc/plant_dist_kernel.h).
+
+``sim_model`` (optional) gives the plant another model than the planner's: mjcf.vary_model's arguments -- mass_scale, com_offset,
+friction_scale, damping_scale, armature_scale, frictionloss_scale -- applied to the env's compiled scene on the plant side only
+(deploy/plant.py: Plant.set_models; csrc/plant_var_kernel.h).  The model's structure and geometry stay the planner's.
 """
 from __future__ import annotations
 
@@ -42,6 +45,9 @@ class DialSimConfig:
     # plant disturbances (sim_disturbance_settings reads it); None: the undisturbed plant
     #   {actuator_gain: float | [nu], actuator_bias: float | [nu], shoves: [{t, duration, dv: [6]}], seed: int, gain_range: [lo, hi]}
     sim_disturbance: Optional[Dict[str, Any]] = None
+    # plant-side model mismatch (sim_model_settings reads it); None: the plant runs the planner's model
+    #   {mass_scale: float | {body: s}, com_offset: {body: [3]}, friction_scale, damping_scale, armature_scale, frictionloss_scale}
+    sim_model: Optional[Dict[str, Any]] = None
 
 
 _DISTURBANCE_KEYS = ("actuator_gain", "actuator_bias", "shoves", "seed", "gain_range")
@@ -77,6 +83,24 @@ def sim_disturbance_settings(block: Dict[str, Any], nu: int):
     return gain, bias, shoves
 
 
+_MODEL_KEYS = ("mass_scale", "com_offset", "friction_scale", "damping_scale", "armature_scale", "frictionloss_scale")
+
+
+def sim_model_settings(block: Dict[str, Any], model: Dict[str, Any]) -> Dict[str, Any]:
+    """A `sim_model` block -> the plant's model: mjcf.vary_model(model, **block).  Raises ValueError on unknown keys and on whatever
+    vary_model refuses (unknown bodies, non-positive scales)."""
+    from dial_mpc_amd.mjcf import vary_model
+    if not isinstance(block, dict):
+        raise ValueError(f"sim_model is a mapping; got {type(block).__name__}")
+    unknown = sorted(set(block) - set(_MODEL_KEYS))
+    if unknown:
+        raise ValueError(f"sim_model: unknown keys {unknown}; known: {list(_MODEL_KEYS)}")
+    try:
+        return vary_model(model, **{k: v for k, v in block.items() if v is not None})
+    except ValueError as e:
+        raise ValueError(f"sim_model: {e}") from None
+
+
 class DialSim:
     def __init__(self, sim_config: DialSimConfig, env_config, dial_config, env, shm_prefix: str = "", device: Optional[int] = None):
         from dial_mpc_amd.utils.io_utils import get_model_path
@@ -98,11 +122,15 @@ class DialSim:
         if not os.path.exists(os.path.splitext(scene)[0] + ".json"):
             print(f"[dial-mpc-sim] scene {sim_config.scene_name} is not a compiled scene of this package: simulating the env's own "
                   f"scene ({type(env).__name__}) at sim_dt = {self.sim_dt}")
+        model_kw = {}
+        if sim_config.sim_model is not None:   # one mismatched model for the one plant (V = 1)
+            model_kw = dict(models=[sim_model_settings(sim_config.sim_model, env.sys.model)], model_of=[0])
+            print(f"[dial-mpc-sim] plant model mismatch: {sim_config.sim_model}")
         if sim_config.sim_disturbance is None:
-            self.plant = Plant(env, self.sim_dt, self.leg_control, M=1, device=device)
+            self.plant = Plant(env, self.sim_dt, self.leg_control, M=1, device=device, **model_kw)
         else:
             gain, bias, shoves = sim_disturbance_settings(sim_config.sim_disturbance, int(env.sys.nu))
-            self.plant = Plant(env, self.sim_dt, self.leg_control, M=1, device=device, disturbance=dict(gain=gain, bias=bias))
+            self.plant = Plant(env, self.sim_dt, self.leg_control, M=1, device=device, disturbance=dict(gain=gain, bias=bias), **model_kw)
             for t, duration, dv in shoves:
                 self.plant.shove(t, duration, dv)
             print(f"[dial-mpc-sim] plant disturbance: actuator gain {np.round(gain, 3).tolist()}, bias {np.round(bias, 3).tolist()}, "

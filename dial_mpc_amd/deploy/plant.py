@@ -9,8 +9,14 @@ Plant disturbances (``dial_set_plant_disturbance``, csrc/plant_dist_kernel.h): p
 gain / bias.  ``event_fires`` restates the kernel's window test, ``disturbance_row`` packs one plant's row, and ``Plant`` binds
 them (``Plant(..., disturbance=)``, ``set_disturbance``, ``shove``).  A kick's ``dv`` is in generalised velocity coordinates and
 the model's units: behind a free base joint dofs 0-2 are the base's linear velocity in the WORLD frame (m/s), dofs 3-5 its angular
-velocity in the BODY frame (rad/s), the rest joint rates.  The plant's constants stay the planner's: masses, inertias, friction and
-geometry are not disturbed (their derived constants would have to be recompiled through mjcf.py).
+velocity in the BODY frame (rad/s), the rest joint rates.
+
+Model mismatch (``dial_set_plant_models``, csrc/plant_var_kernel.h): per plant, another set of model constants -- masses, inertias,
+centres of mass, sliding friction, damping, armature, friction loss (``mjcf.vary_model`` makes such variants and recomputes what
+derives from them).  ``Plant(..., models=[...], model_of=[...])`` / ``set_models`` bind V variants and the index that picks one per
+plant; the planner's model is untouched.  Kicks and actuator errors combine with it.  Still the planner's: the structure of the
+model (bodies, joints, the contact list) and its geometry (geom sizes and positions) -- a payload body or another foot radius is
+another compiled scene.
 """
 from __future__ import annotations
 
@@ -113,9 +119,13 @@ class Plant:
     control law (control_hip) has a third mode, "law": the rows are normalised actions and the law runs at every sim step from the
     plant's current state (DIAL_PLANT_LAW; law_step is the step counter it sees)."""
 
-    def __init__(self, env, sim_dt: float, leg_control: str = "torque", M: int = 1, device: Optional[int] = None, disturbance=None):
+    def __init__(self, env, sim_dt: float, leg_control: str = "torque", M: int = 1, device: Optional[int] = None, disturbance=None,
+                 models=None, model_of=None):
         """disturbance: None (the undisturbed plant, the context and kernels as they were), True (a context that can take
-        disturbances: set_disturbance / shove later) or a dict of set_disturbance's arguments (gain, bias, events), bound at once."""
+        disturbances: set_disturbance / shove later) or a dict of set_disturbance's arguments (gain, bias, events), bound at once.
+        models: None (every plant runs the env's own model), True (a context that can take per-plant models: set_models later; only a
+        custom environment needs to know in advance, it picks another plugin) or a list of model dicts with model_of, bound at once
+        (set_models' arguments)."""
         import torch
         from dial_mpc_amd import _lib
         from dial_mpc_amd.envs.custom_env import CustomEnv, torque_joint_convention
@@ -138,7 +148,11 @@ class Plant:
         self.ctrl_dt = float(env._config.dt)
         self._hold = _lib.PLANT_HOLD_FIRST
         self._dist_capable = disturbance is not None and disturbance is not False
-        self.ctx = env.make_plant(self.sim_dt, device=device, disturbance=True) if self._dist_capable else env.make_plant(self.sim_dt, device=device)
+        self._models_capable = (models is not None and models is not False) or not custom
+        kw = dict(disturbance=True) if self._dist_capable else {}
+        if models is not None and models is not False:
+            kw["models"] = True
+        self.ctx = env.make_plant(self.sim_dt, device=device, **kw)
         self.nq, self.nv, self.nu = self.ctx.nq, self.ctx.nv, self.ctx.nu
         self.width = 1 + self.nq + self.nv + self.nu          # trace / record row: [t, qpos, qvel, ctrl]
         self.dev = self.ctx.torch_device
@@ -149,6 +163,31 @@ class Plant:
         self.reset()
         if isinstance(disturbance, dict):
             self.set_disturbance(**disturbance)
+        self.model_of = None                 # int32 [M] while plant models are bound
+        if models is not None and models is not False and models is not True:
+            self.set_models(models, model_of)
+
+    # ---- model mismatch (dial_set_plant_models)
+    def set_models(self, models, model_of=None):
+        """Bind per-plant models: `models` a list of V compiled model dicts (mjcf.vary_model(env.sys.model, ...)), `model_of` [M]
+        indices into it (None: V == M, plant b runs model b).  Each dict gets timestep = sim_dt, as make_plant gives the env's own
+        model.  models None unbinds: every plant runs the env's model again.  reset() keeps the binding.  Returns the index bound."""
+        if models is None:
+            self.ctx.set_plant_models(None)
+            self.model_of = None
+            return None
+        if not self._models_capable:
+            raise ValueError("this Plant of a custom environment was created without per-plant models: pass models=True (or the list) to Plant")
+        from dial_mpc_amd import _lib
+        models = list(models)
+        index = _lib.plant_model_index(model_of, len(models), self.M)
+        structs = []
+        for m in models:
+            st = _abi.make_model(m)
+            st.timestep = float(self.sim_dt)
+            structs.append(st)
+        self.model_of = self.ctx.set_plant_models(structs, index)
+        return self.model_of
 
     # ---- disturbances (dial_set_plant_disturbance)
     def _per_plant(self, x, what):
@@ -227,7 +266,7 @@ class Plant:
 
     def reset(self):
         """Every plant at the env's initial pose (the home keyframe; env.reset's), zero velocity, t = 0.  A bound disturbance stays
-        bound (its windows are on the clock that starts again at 0)."""
+        bound (its windows are on the clock that starts again at 0), and so do bound plant models."""
         torch = self._torch
         q0 = np.asarray(self.env._init_q, np.float32)
         qpos = torch.as_tensor(np.tile(q0, (self.M, 1)), device=self.dev)

@@ -186,11 +186,12 @@ class BaseEnv:
     def make_model(self) -> "_abi.DialModel":
         return _abi.make_model(self.sys.model)
 
-    def make_plant(self, sim_dt: float, device: Optional[int] = None, disturbance: bool = False):
+    def make_plant(self, sim_dt: float, device: Optional[int] = None, disturbance: bool = False, models: bool = False):
         """The context of the plant simulator (deploy/plant.py, dial_plant_step): this env's compiled scene with timestep = sim_dt,
         and its task with one physics step per step (n_frames = 1, dt = sim_dt).  Nothing else of the physics changes.
         disturbance: the context will have plant disturbances bound (set_plant_disturbance) -- nothing to prepare for the built-in
-        families (libdialplantdist.so serves them); a custom environment picks another plugin."""
+        families (libdialplantdist.so serves them); a custom environment picks another plugin.  models: the context will have
+        per-plant models bound (set_plant_models) -- likewise (libdialplantvar.so)."""
         from dial_mpc_amd import _lib
         model = self.make_model()
         model.timestep = float(sim_dt)

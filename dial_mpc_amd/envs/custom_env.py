@@ -120,10 +120,20 @@ class CustomEnv(BaseEnv):
             self._plugin = build_plugin(self.sys.model, self.reward_source(), control_src=self.control_source())
         return self._plugin
 
-    def plant_plugin_path(self, disturbance: bool = False) -> str:
+    def plant_plugin_path(self, disturbance: bool = False, models: bool = False) -> str:
         """Build (or find in the cache) this env's task plugin WITH the plant simulator's kernel (build_plugin(plant=True)): the plugin
         of make_plant's context.  Another library than plugin_path()'s, which stays as it is.  disturbance=True: the plugin that also
-        carries the disturbed plant kernel (build_plugin(plant_disturbance=True)), a third library."""
+        carries the disturbed plant kernel (build_plugin(plant_disturbance=True)), a third library.  models=True: the plugin that
+        carries the plant kernel with per-plant model constants (build_plugin(plant_models=True)), with disturbance=True both."""
+        if models:
+            cache = getattr(self, "_plant_var_plugins", None)
+            if cache is None:
+                cache = self._plant_var_plugins = {}
+            if bool(disturbance) not in cache:
+                from dial_mpc_amd.plugin import build_plugin
+                cache[bool(disturbance)] = build_plugin(self.sys.model, self.reward_source(), control_src=self.control_source(),
+                                                        plant_disturbance=bool(disturbance), plant_models=True)
+            return cache[bool(disturbance)]
         if disturbance:
             if getattr(self, "_plant_dist_plugin", None) is None:
                 from dial_mpc_amd.plugin import build_plugin
@@ -135,16 +145,17 @@ class CustomEnv(BaseEnv):
             self._plant_plugin = build_plugin(self.sys.model, self.reward_source(), control_src=self.control_source(), plant=True)
         return self._plant_plugin
 
-    def make_plant(self, sim_dt: float, device: Optional[int] = None, disturbance: bool = False):
+    def make_plant(self, sim_dt: float, device: Optional[int] = None, disturbance: bool = False, models: bool = False):
         """The context of the plant simulator (deploy/plant.py, dial_plant_step) of this env: its model with timestep = sim_dt, its
         task with one physics step per step (n_frames = 1, dt = sim_dt), on the plant-enabled plugin with the env's parameters and
-        reference table.  disturbance=True: on the plugin that also carries the disturbed kernel (set_plant_disturbance needs it)."""
+        reference table.  disturbance=True: on the plugin that also carries the disturbed kernel (set_plant_disturbance needs it);
+        models=True: on the plugin that carries the per-plant-model kernel (set_plant_models needs it)."""
         from dial_mpc_amd import _lib
         model = self.make_model()
         model.timestep = float(sim_dt)
         task = self.make_task()
         task.n_frames, task.dt = 1, float(sim_dt)
-        return _lib.Context(model, task, None, self._device_or(device), **self.context_kwargs(plant=True, disturbance=disturbance))
+        return _lib.Context(model, task, None, self._device_or(device), **self.context_kwargs(plant=True, disturbance=disturbance, models=models))
 
     def control(self, state, acts):
         """The control law for T actions from one state, in one launch: acts [T, nu] (or [nu]) -> device tensor [T, nu] of what the
@@ -183,12 +194,13 @@ class CustomEnv(BaseEnv):
         t = self._table_override if getattr(self, "_table_override", None) is not None else self.make_table()
         return None if t is None else _lib.user_table_array(t)
 
-    def context_kwargs(self, plant: bool = False, disturbance: bool = False) -> Dict[str, Any]:
+    def context_kwargs(self, plant: bool = False, disturbance: bool = False, models: bool = False) -> Dict[str, Any]:
         """What a _lib.Context of this env needs beyond (model, task, cfg): its plugin (plant=True: the plant-enabled one, with
-        disturbance=True the one that also carries the disturbed plant kernel), parameters and reference table."""
+        disturbance=True the one that also carries the disturbed plant kernel, with models=True the per-plant-model kernel),
+        parameters and reference table."""
         from dial_mpc_amd import _lib
-        plant = plant or disturbance
-        kw = dict(plugin=self.plant_plugin_path(disturbance) if plant else self.plugin_path(), user_params=self.user_param_vector())
+        plant = plant or disturbance or models
+        kw = dict(plugin=self.plant_plugin_path(disturbance, models) if plant else self.plugin_path(), user_params=self.user_param_vector())
         table = self._table()
         if table is not None:
             kw.update(user_table=table, table_row0=int(self.table_row0), table_mode=_lib.table_mode(self.table_mode))

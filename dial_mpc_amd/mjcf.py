@@ -16,6 +16,7 @@ Everything is fp64 NumPy on the host; the result is a dict whose keys are the fi
 """
 from __future__ import annotations
 
+import copy
 import json
 import math
 import os
@@ -907,6 +908,87 @@ def _set_const(m: Dict[str, Any]) -> None:
         else:
             diw[da] = Minv[da, da]
     m["dof_invweight0"] = diw
+
+
+# ------------------------------------------------------------------ model mismatch
+def _positive_scale(x, what: str) -> np.ndarray:
+    a = np.asarray(x, dtype=np.float64)
+    if not (np.isfinite(a).all() and (a > 0).all()):
+        raise ValueError(f"{what}: scales must be finite and > 0; got {x!r}")
+    return a
+
+
+def _body_index(m: Dict[str, Any], body) -> int:
+    nb = int(m["nbody"])
+    if isinstance(body, str):
+        names = list(m.get("names", {}).get("body", []))
+        if body not in names:
+            raise ValueError(f"unknown body {body!r}; the model's bodies: {names}")
+        return names.index(body)
+    if isinstance(body, (bool, float)) or not isinstance(body, (int, np.integer)) or not 0 <= int(body) < nb:
+        raise ValueError(f"unknown body {body!r}; a name or an index in 0 .. {nb - 1}")
+    return int(body)
+
+
+def vary_model(m: Dict[str, Any], *, mass_scale=None, com_offset=None, friction_scale=None, damping_scale=None, armature_scale=None,
+               frictionloss_scale=None) -> Dict[str, Any]:
+    """A copy of the compiled model `m` with varied constants -- the plant side of a model mismatch (deploy/plant.py:
+    Plant(models=), dial_set_plant_models); `m` itself is not touched.  Bodies are addressed by index or by m["names"]["body"].
+      mass_scale          a scalar (every body) or {body: s}: body_mass and body_inertia of that body times s (a change of density)
+      com_offset          {body: d[3]}: d is added to body_ipos (the body's centre of mass, in the body's frame, metres)
+      friction_scale      a scalar (every contact) or {contact slot: s} on con_friction[:, 0:2] (the sliding coefficients)
+      damping_scale       a scalar or [nv] on dof_damping
+      armature_scale      a scalar or [nv] on dof_armature
+      frictionloss_scale  a scalar or [nfri] on fri_loss
+    Then meaninertia, body_invweight0 and dof_invweight0 are recomputed from the varied model (_set_const), as compile_mjcf does.
+    Raises ValueError on non-finite or non-positive scales, non-finite offsets, unknown bodies or contact slots and other shapes.
+    No structural change: every dimension, the trees and the contact list stay.  Adding a payload body and changing geom sizes
+    are out of scope (both change what the kernels are instantiated or their tables are sized for: compile another MJCF)."""
+    out = {k: (v.copy() if isinstance(v, np.ndarray) else copy.deepcopy(v)) for k, v in m.items()}
+    nb, nv, ncon, nfri = int(m["nbody"]), int(m["nv"]), int(m["ncon"]), int(m.get("nfri", 0))
+    for k in ("body_mass", "body_inertia", "body_ipos", "con_friction", "dof_damping", "dof_armature"):
+        out[k] = np.array(out[k], dtype=np.float64)
+    if mass_scale is not None:
+        if isinstance(mass_scale, dict):
+            s = np.ones(nb)
+            for body, v in mass_scale.items():
+                s[_body_index(m, body)] = float(_positive_scale(v, f"mass_scale[{body!r}]").reshape(()))
+        else:
+            s = np.broadcast_to(_positive_scale(mass_scale, "mass_scale").reshape(()), (nb,))
+        out["body_mass"] = out["body_mass"] * s
+        out["body_inertia"] = out["body_inertia"] * s[:, None]
+    if com_offset is not None:
+        if not isinstance(com_offset, dict):
+            raise ValueError("com_offset is {body: d[3]}")
+        for body, d in com_offset.items():
+            d = np.asarray(d, dtype=np.float64)
+            if d.shape != (3,) or not np.isfinite(d).all():
+                raise ValueError(f"com_offset[{body!r}]: three finite metres are needed; got {d!r}")
+            out["body_ipos"][_body_index(m, body)] += d
+    if friction_scale is not None:
+        if isinstance(friction_scale, dict):
+            s = np.ones(ncon)
+            for c, v in friction_scale.items():
+                if isinstance(c, (bool, float, str)) or not 0 <= int(c) < ncon:
+                    raise ValueError(f"friction_scale: unknown contact slot {c!r}; the model has {ncon}")
+                s[int(c)] = float(_positive_scale(v, f"friction_scale[{c!r}]").reshape(()))
+        else:
+            s = np.broadcast_to(_positive_scale(friction_scale, "friction_scale").reshape(()), (ncon,))
+        out["con_friction"][:, 0:2] = out["con_friction"][:, 0:2] * s[:, None]
+
+    def per(key, scale, n, what):
+        a = _positive_scale(scale, what)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+            raise ValueError(f"{what}: a scalar or [{n}] values; got shape {a.shape}")
+        out[key] = np.array(out[key], dtype=np.float64) * np.broadcast_to(a, (n,))
+    if damping_scale is not None:
+        per("dof_damping", damping_scale, nv, "damping_scale")
+    if armature_scale is not None:
+        per("dof_armature", armature_scale, nv, "armature_scale")
+    if frictionloss_scale is not None:
+        per("fri_loss", frictionloss_scale, nfri, "frictionloss_scale")
+    _set_const(out)
+    return out
 
 
 # ------------------------------------------------------------------ (de)serialisation

@@ -11,7 +11,9 @@ exports ``TABLE_SYMBOL``, the host function behind the reference table (``dial_s
 the built-in families' kernel, behind the table of ``csrc/plant_plugin.h``;
 ``dial_plant_step`` on the plugin's contexts) and a fourth symbol (``PLANT_SYMBOL``); a plugin built without it is unchanged.
 ``plant_disturbance=True`` (implies ``plant=True``) adds the disturbed plant kernel (``plant_dist_kernel`` of
-``csrc/plant_dist_kernel.h``; ``dial_set_plant_disturbance``) and a fifth symbol (``PLANT_DIST_SYMBOL``).  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
+``csrc/plant_dist_kernel.h``; ``dial_set_plant_disturbance``) and a fifth symbol (``PLANT_DIST_SYMBOL``).
+``plant_models=True`` (implies ``plant=True``) adds the plant kernel with per-plant model constants (``plant_var_kernel`` of
+``csrc/plant_var_kernel.h``; ``dial_set_plant_models``) and a sixth symbol (``PLANT_VAR_SYMBOL``).  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
 hashes every csrc source, ``include/dial_mpc.h``, the reward, the control law (when there is one), the dimensions, the flags and ``hipcc --version``.  hipcc
 cross-compiles, so building needs no GPU.
 """
@@ -36,6 +38,7 @@ CTRL_SYMBOL = "dial_plugin_ctrl_v1"   # exported only by a plugin built with a c
 TABLE_SYMBOL = "dial_plugin_table_v1"  # exported by every plugin: the reference table's host function (dial_set_user_table)
 PLANT_SYMBOL = "dial_plugin_plant_v1"  # exported only by a plugin built with plant=True: the plant kernel's table (dial_plant_step)
 PLANT_DIST_SYMBOL = "dial_plugin_plant_dist_v1"  # only with plant_disturbance=True: the disturbed plant kernel's table (dial_set_plant_disturbance)
+PLANT_VAR_SYMBOL = "dial_plugin_plant_var_v1"  # only with plant_models=True: the per-plant-model plant kernel's table (dial_set_plant_models)
 DIM_NAMES = ("nq", "nv", "nu", "nbody", "njnt", "ngeom", "nsite", "ncon", "nlim", "nfri")
 _DIM_MACROS = ("NQ", "NV", "NU", "NB", "NJ", "NG", "NS", "NC", "NL", "NFRI")
 
@@ -119,21 +122,26 @@ def plugin_key(model, reward_src: str, flags: Sequence[str], control_src: Option
 
 
 def build_plugin(model, reward_src: str, flags: Optional[Sequence[str]] = None, verbose: bool = False,
-                 control_src: Optional[str] = None, plant: bool = False, plant_disturbance: bool = False) -> str:
+                 control_src: Optional[str] = None, plant: bool = False, plant_disturbance: bool = False,
+                 plant_models: bool = False) -> str:
     """Compile (or find in the cache) the task plugin of `model` with the reward `reward_src` (HIP source text, or the path of a
     .hip file) and, optionally, the control law `control_src` (the same two forms) -> path of the shared library.  plant=True:
     the plugin also carries the plant simulator's kernel (-DDIAL_PLUGIN_PLANT=1; the define is one of the flags the cache key
     hashes, so it is another library than the plugin without it).  plant_disturbance=True implies plant=True and adds the disturbed
     plant kernel (-DDIAL_PLUGIN_PLANT_DIST=1 after it: csrc/plant_dist_kernel.h, one kernel and one symbol more, again another library;
-    the plugins built with plant=True or with neither keep their flags and keys).  A compile error in either source raises DialHipError with
+    the plugins built with plant=True or with neither keep their flags and keys).  plant_models=True implies plant=True too and adds
+    the plant kernel with per-plant model constants (-DDIAL_PLUGIN_PLANT_VAR=1, last: csrc/plant_var_kernel.h, one kernel and one symbol
+    more; it combines with plant_disturbance=True, and the plugins built without it keep their flags and keys).  A compile error in either source raises DialHipError with
     hipcc's own message."""
     import fcntl
     check_model(model)
     flags = list(_COMMON + _FAST if flags is None else flags)
-    if plant or plant_disturbance:
+    if plant or plant_disturbance or plant_models:
         flags.append("-DDIAL_PLUGIN_PLANT=1")
     if plant_disturbance:
         flags.append("-DDIAL_PLUGIN_PLANT_DIST=1")
+    if plant_models:
+        flags.append("-DDIAL_PLUGIN_PLANT_VAR=1")
     reward = _read_reward(reward_src)
     control = None if control_src is None else _read_reward(control_src)
     key = plugin_key(model, reward, flags, control)[:24]

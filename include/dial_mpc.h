@@ -73,6 +73,7 @@ extern "C" {
  * gain[nu] | bias[nu] | E x { t0, t1, dv[nv] } */
 #define DIAL_PLANT_MAX_EVENTS 16
 #define DIAL_PLANT_DIST_ROW(nu, nv, E) (2 * (nu) + (E) * (2 + (nv)))
+#define DIAL_MAX_PLANT_MODELS 1024 /* dial_set_plant_models: distinct plant models of one binding */
 
 /* joint types (MuJoCo numbering) */
 #define DIAL_JNT_FREE 0
@@ -637,14 +638,36 @@ int dial_plant_step(dial_ctx* ctx, float* states, double* t, const float* plan_t
  *   2. Actuator error: the mode's ctrl c -- the DIAL_PLANT_CTRL row, the DIAL_PLANT_PD torque after its clip, the DIAL_PLANT_LAW
  *      value -- becomes fma(gain[a], c, bias[a]) (one rounding).  The trace records that value; the actuators apply it like any
  *      ctrl, their own ctrlrange clip included.
- * gain = 1, bias = 0 and no firing event give the undisturbed plant bit for bit.  The plant's constants are still the planner's:
- * masses, inertias, friction and geometry are NOT disturbed (that needs the model's derived constants recompiled).
+ * gain = 1, bias = 0 and no firing event give the undisturbed plant bit for bit.  The plant's constants are not touched here:
+ * masses, inertias and friction are varied per plant by dial_set_plant_models (below), which combines with this call.
  * dist == NULL with M == 0 and n_events == 0 unbinds: dial_plant_step takes the undisturbed path again.  No synchronisation.
  * Fails with DIAL_ERR_ARG and a message that starts with "dial_set_plant_disturbance: " on a null context, n_events outside
  * 0 .. DIAL_PLANT_MAX_EVENTS, M < 1 or M > DIAL_MAX_PLANTS with a non-NULL buffer, a NULL buffer with M or n_events != 0;
  * with DIAL_ERR_UNSUPPORTED when libdialplantdist.so is missing or stale, on a task plugin without the table, and in the IEEE
  * measurement build.  dial_plant_step fails with DIAL_ERR_ARG when its M differs from the bound M. */
 int dial_set_plant_disturbance(dial_ctx* ctx, const float* dist, int M, int n_events);
+/* Plant model mismatch: per-plant model constants.  models:[V] and model_of:[M] are HOST arrays, 1 <= V <= DIAL_MAX_PLANT_MODELS,
+ * 1 <= M <= DIAL_MAX_PLANTS, 0 <= model_of[b] < V.  The library COPIES them: it builds V blocks of kernel constants -- what
+ * dial_create builds from a model, with the context's task and options; on a task-plugin context with the context's current user
+ * parameters and reference-table binding -- and uploads them, with the index, into buffers the context owns (dial_destroy and a
+ * re-bind free them).  While bound, dial_plant_step requires M == the bound M and runs the kernel of csrc/plant_var_kernel.h (in
+ * libdialplantvar.so next to this library; on a task-plugin context the plugin's own, build_plugin(plant_models=True), behind the
+ * optional table dial_plugin_plant_var_v1): plant b stages the constants of models[model_of[b]] instead of the context's, and
+ * everything else -- clock, row rule, control modes, trace, a bound disturbance (dial_set_plant_disturbance) -- is as documented
+ * above.  Plant b of such a launch equals, bit for bit, the plant of a context created from models[model_of[b]].
+ * A model is accepted when dial_create would build it and pick the context's kernel instantiation for it (same dimensions and dof
+ * tree, the same limits of the instantiation's tables), its timestep equals the context's, and nu, act_isposition, act_qposadr,
+ * act_dofadr, jnt_type[0] and jnt_qposadr[0] equal the context's model's (dial_plant_step's checks read them).  What may differ is
+ * every float: masses, inertias, centres of mass, friction, damping, armature, friction loss, gains of the solver's impedance rows.
+ * (NULL, 0, NULL, 0) unbinds: dial_plant_step runs the context's own model again.  A failed call leaves the previous binding in
+ * place.  While models are bound, dial_set_user_params and dial_set_user_table fail with DIAL_ERR_ARG (unbind first: the blocks
+ * carry a copy of both).  Synchronises the device.
+ * Fails with DIAL_ERR_ARG and a message that starts with "dial_set_plant_models: " on a null context, V outside
+ * 1 .. DIAL_MAX_PLANT_MODELS, M outside 1 .. DIAL_MAX_PLANTS, a null pointer with non-zero counts, an index outside 0 .. V - 1, a
+ * rejected model (the message names its index and the reason); with DIAL_ERR_UNSUPPORTED when libdialplantvar.so is missing or
+ * stale, on a task plugin without the table, and in the IEEE measurement build.  dial_plant_step fails with DIAL_ERR_ARG when its
+ * M differs from the bound M. */
+int dial_set_plant_models(dial_ctx* ctx, const dial_model* models, int V, const int32_t* model_of, int M);
 
 /* ABI self-description used by tests: sizeof of the three structs. */
 int dial_abi_sizes(int* model_bytes, int* task_bytes, int* cfg_bytes);
