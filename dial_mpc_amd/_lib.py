@@ -75,6 +75,7 @@ def build(force: bool = False, verbose: bool = False, ieee: bool = False) -> str
         build_plant(force=force, verbose=verbose)
         build_plant_dist(force=force, verbose=verbose)
         build_plant_var(force=force, verbose=verbose)
+        build_plan_var(force=force, verbose=verbose)
     return _build_lib(IEEE_LIB_PATH if ieee else LIB_PATH, [(os.path.join(_CSRC, "dial_hip.hip"), [], "dial_hip.o")] +
                       [(os.path.join(_CSRC, "kern_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []), f"kern_family_{k}.o")
                        for k in range(N_FAMILIES)], force, verbose, ieee)
@@ -114,6 +115,18 @@ def build_plant_var(force: bool = False, verbose: bool = False) -> str:
     time plant models are bound."""
     return _build_lib(PLANT_VAR_LIB_PATH, [(os.path.join(_CSRC, "plant_var_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []),
                                             f"plant_var_family_{k}.o") for k in range(N_PLANT_FAMILIES)], force, verbose, False)
+
+
+PLAN_VAR_LIB_PATH = os.path.join(_CSRC, "libdialplanvar.so")
+
+
+def build_plan_var(force: bool = False, verbose: bool = False) -> str:
+    """libdialplanvar.so: the rollout kernel with per-plan / per-sample model constants (csrc/plan_var_kernel.h: dial_set_plan_models)
+    once per robot family (plan_var_family.hip -DDIAL_FAMILY=k, build_plant's flags), a library of its own so that the code objects of
+    libdialhip.so and the plant libraries stay as shipped.  libdialhip.so loads it from its own directory the first time planner
+    models are bound."""
+    return _build_lib(PLAN_VAR_LIB_PATH, [(os.path.join(_CSRC, "plan_var_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []),
+                                           f"plan_var_family_{k}.o") for k in range(N_PLANT_FAMILIES)], force, verbose, False)
 
 
 def _build_lib(out: str, units, force: bool, verbose: bool, ieee: bool) -> str:
@@ -251,6 +264,11 @@ def load(path: Optional[str] = None):
     except AttributeError:
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack per-plant models)
             raise
+    try:
+        lib.dial_set_plan_models.argtypes = [vp, vp, ci, vp, ci, ci]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack planner models)
+            raise
     lib.dial_env_reset.argtypes = [vp, fp, fp, fp, fp, fp, vp]
     lib.dial_env_reset_batch.argtypes = [vp, fp, fp, fp, fp, fp, ci, vp]
     lib.dial_status.argtypes = [vp]
@@ -278,7 +296,8 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
             "dial_status", "dial_set_timing", "dial_get_rollout_ms", "dial_abi_sizes",
             "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch",
             "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params", "dial_plant_step", "dial_user_control",
-            "dial_set_user_table", "dial_set_plant_disturbance", "dial_set_plant_models")
+            "dial_set_user_table", "dial_set_plant_disturbance", "dial_set_plant_models",
+            "dial_set_plan_models")
 
 # dial_plant_step flags (include/dial_mpc.h)
 PLANT_CTRL, PLANT_PD, PLANT_HOLD_FIRST = (_abi.MACROS[k] for k in ("DIAL_PLANT_CTRL", "DIAL_PLANT_PD", "DIAL_PLANT_HOLD_FIRST"))
@@ -311,6 +330,36 @@ def plant_model_index(model_of, V: int, M: Optional[int] = None) -> np.ndarray:
                          f"shape {a.shape}, dtype {a.dtype}")
     if a.min() < 0 or a.max() >= V:
         raise ValueError(f"plant models: model_of holds indices outside 0 .. V - 1 = {V - 1}")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+MAX_PLAN_MODELS = _abi.MACROS["DIAL_MAX_PLAN_MODELS"]   # distinct planner models of one binding (dial_set_plan_models)
+PLAN_MODEL_MODES = {"plan": _abi.MACROS["DIAL_PLAN_MODELS_PER_PLAN"], "sample": _abi.MACROS["DIAL_PLAN_MODELS_PER_SAMPLE"]}
+
+
+def plan_model_index(model_of, V: int, rows: int, per: str = "plan") -> np.ndarray:
+    """The index dial_set_plan_models takes: contiguous int32 [rows] with 0 <= model_of[r] < V.  per="plan": one row per plan (rows =
+    the plans the binding serves, at most the context's plan capacity), default row g = g % V.  per="sample": rows = Nsample + 1, one
+    row per noisy sample and the mean trajectory's last; default n % V for the noisy samples and 0 for the mean trajectory.  Raises
+    ValueError on an unknown `per`, another shape, a non-integer or an index out of range."""
+    if per not in PLAN_MODEL_MODES:
+        raise ValueError(f"plan models: per = {per!r}; 'plan' or 'sample' are allowed")
+    V, rows = int(V), int(rows)
+    if not 1 <= V <= MAX_PLAN_MODELS:
+        raise ValueError(f"plan models: {V} models; 1 .. DIAL_MAX_PLAN_MODELS = {MAX_PLAN_MODELS} are allowed")
+    if rows < 1 or (per == "plan" and rows > _abi.MACROS["DIAL_MAX_PLANS"]) or (per == "sample" and rows < 2):
+        raise ValueError(f"plan models: {rows} rows; per plan 1 .. DIAL_MAX_PLANS = {_abi.MACROS['DIAL_MAX_PLANS']}, per sample Nsample + 1 >= 2")
+    if model_of is None:
+        a = np.arange(rows, dtype=np.int32) % V
+        if per == "sample":
+            a[rows - 1] = 0   # the mean trajectory: the first model
+        return a
+    a = np.asarray(model_of)
+    if a.ndim != 1 or a.size != rows or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"plan models: model_of is an integer list of {rows} entries (per {per}: "
+                         f"{'one per plan' if per == 'plan' else 'Nsample + 1, the mean trajectory last'}); got shape {a.shape}, dtype {a.dtype}")
+    if a.min() < 0 or a.max() >= V:
+        raise ValueError(f"plan models: model_of holds indices outside 0 .. V - 1 = {V - 1}")
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
@@ -616,6 +665,32 @@ class Context:
             ctypes.memmove(ctypes.addressof(arr[v]), ctypes.addressof(struct), ctypes.sizeof(_abi.DialModel))
         self._check(self.lib.dial_set_plant_models(self.h, ctypes.addressof(arr), len(models), index.ctypes.data, int(index.size)),
                     "dial_set_plant_models")
+        return index
+
+    def set_plan_models(self, models, model_of=None, per: str = "plan"):
+        """Bind planner models (dial_set_plan_models): `models` a list of V compiled model dicts or DialModel structs -- variants of
+        this context's model with the same structure and timestep (mjcf.vary_model makes them).  per="plan": `model_of` [rows <=
+        plan_cap], every rollout of plan g of a grouped launch runs models[model_of[g]] (None: one row per plan of the context's plan
+        capacity, g % V); one-plan launches read row 0.  per="sample": `model_of` [Nsample + 1], rollout n of every plan runs
+        models[model_of[n]], the last row is the mean trajectory's (None: n % V, the mean trajectory model 0).  The library copies
+        both.  While bound, rollout / reverse_once* / reverse_once_batch* run the per-model rollout kernel; env_step*, env_reset* and
+        plant_step ignore the binding.  models None unbinds.  Returns the index."""
+        if models is None:
+            self._check(self.lib.dial_set_plan_models(self.h, None, 0, None, 0, 0), "dial_set_plan_models")
+            return None
+        models = list(models)
+        if per not in PLAN_MODEL_MODES:
+            raise ValueError(f"plan models: per = {per!r}; 'plan' or 'sample' are allowed")
+        if self.cfg is None:
+            raise ValueError("plan models: the context was created without a dial_cfg (it launches no rollouts)")
+        rows = self.cfg.Nsample + 1 if per == "sample" else (len(model_of) if model_of is not None else self.plan_cap)
+        index = plan_model_index(model_of, len(models), rows, per)
+        arr = (_abi.DialModel * len(models))()
+        for v, m in enumerate(models):
+            struct = m if isinstance(m, _abi.DialModel) else _abi.make_model(m)   # (kept alive across the copy)
+            ctypes.memmove(ctypes.addressof(arr[v]), ctypes.addressof(struct), ctypes.sizeof(_abi.DialModel))
+        self._check(self.lib.dial_set_plan_models(self.h, ctypes.addressof(arr), len(models), index.ctypes.data, int(index.size),
+                                                  PLAN_MODEL_MODES[per]), "dial_set_plan_models")
         return index
 
     # ---- K3

@@ -39,12 +39,15 @@ def softmax_update(weights, Y0s, sigma, mu_0t):
 
 class MBDPI:
     def __init__(self, args: DialConfig, env, device: Optional[int] = None, kernel_rng: bool = False,
-                 force_sharded: bool = False, options: Optional[dict] = None, n_plans: int = 1):
+                 force_sharded: bool = False, options: Optional[dict] = None, n_plans: int = 1,
+                 models=None, model_of=None, model_per: str = "plan"):
         """kernel_rng=True: the noise is generated inside the rollout kernel (Philox keyed by args.seed and a call
         counter) instead of by torch.randn -- the production setting; parity runs pass `eps` explicitly.
         force_sharded (measurement hook): run the sharded code path, collectives included, on a 1-rank process group.
         options: `dial_options` fields for the context (launch-shape / measurement switches, include/dial_mpc.h).
-        n_plans: plans one reverse_once_batch call may carry (the context's dial_options.plan_cap)."""
+        n_plans: plans one reverse_once_batch call may carry (the context's dial_options.plan_cap).
+        models / model_of / model_per: planner models bound at creation (set_models); a custom environment's context is then created on
+        the plugin that carries the per-model rollout kernel (CustomEnv.plugin_path(plan_models=True))."""
         import torch
         self.kernel_rng = bool(kernel_rng)
         self._rng_counter = 0
@@ -79,7 +82,9 @@ class MBDPI:
         if self.n_plans > 1:
             options = dict(options or {}, plan_cap=self.n_plans)
         # a rank's rollout scratch is sized by its own shard, not by the global sample count
-        extra = env.context_kwargs() if hasattr(env, "context_kwargs") else {}   # (custom envs: their task plugin, envs/custom_env.py)
+        extra = {}
+        if hasattr(env, "context_kwargs"):   # (custom envs: their task plugin, envs/custom_env.py)
+            extra = env.context_kwargs(plan_models=True) if models is not None else env.context_kwargs()
         self.ctx = _lib.Context(env.make_model(), env.make_task(), self.cfg, device,
                                 n_local_cap=None if self.world == 1 else self._per, options=options, **extra)
         if hasattr(env, "bind_device"):
@@ -91,6 +96,33 @@ class MBDPI:
         self.step_nodes = torch.as_tensor(self.step_nodes_np, dtype=torch.float32, device=dev)
         self.W = torch.as_tensor(spline.node2u_matrix(args.Hsample, args.Hnode), dtype=torch.float32, device=dev)
         self.V = torch.as_tensor(spline.u2node_matrix(args.Hsample, args.Hnode), dtype=torch.float32, device=dev)
+        self.model_of = None
+        if models is not None:
+            self.set_models(models, model_of, model_per)
+
+    # ---- planner model ensembles (dial_set_plan_models; csrc/plan_var_kernel.h)
+    def set_models(self, models, model_of=None, per: str = "plan"):
+        """Bind planner models: `models` a list of V compiled model dicts (mjcf.vary_model(env.sys.model, ...)).  per="plan": plan g of
+        reverse_once_batch plans with models[model_of[g]] (`model_of` [n_plans]; None: g % V), reverse_once with models[model_of[0]].
+        per="sample": rollout n of every plan runs models[model_of[n]] (`model_of` [Nsample + 1], the mean trajectory last; None:
+        n % V, the mean trajectory model 0) -- domain-randomised sampling.  Every dict gets the env's timestep.  env.step and the
+        plant keep their own model.  models None unbinds.  Returns the index bound."""
+        if models is None:
+            self.ctx.set_plan_models(None)
+            self.model_of = None
+            return None
+        if self.world > 1 or self._force_sharded:
+            raise NotImplementedError("set_models: planner models run on one rank (sharded contexts are not supported)")
+        dt = float(self.env.make_model().timestep)
+        structs = []
+        for m in models:
+            st = _abi.make_model(m)
+            st.timestep = dt
+            structs.append(st)
+        rows = self.args.Nsample + 1 if per == "sample" else self.n_plans
+        index = _lib.plan_model_index(model_of, len(structs), rows, per)
+        self.model_of = self.ctx.set_plan_models(structs, index, per)
+        return self.model_of
 
     # ---- spline maps (constant matrices; dial_core.py:82-101)
     def node2u(self, nodes):
@@ -263,6 +295,48 @@ def load_dial_and_env(config_dict: Dict[str, Any]):
     return dial_config, env_config, env
 
 
+_PLAN_MODEL_KEYS = ("per", "variants", "model_of")
+
+
+def plan_models_settings(block: Dict[str, Any], model: Dict[str, Any], n_plans: int, Nsample: int):
+    """A `plan_models` block of the driver's YAML -> (models, model_of, per) for MBDPI(models=, model_of=, model_per=):
+        per: plan | sample            (default plan)
+        variants: [ {...}, ... ]      each entry the keywords of mjcf.vary_model; {} is the env's model
+        model_of: [...]               optional; n_plans entries per plan, Nsample + 1 per sample (the mean trajectory last)
+    Raises ValueError on unknown keys, an empty variant list, whatever vary_model refuses and an index of the wrong length or range."""
+    from dial_mpc_amd.deploy.dial_sim import sim_model_settings
+    if not isinstance(block, dict):
+        raise ValueError(f"plan_models is a mapping; got {type(block).__name__}")
+    unknown = sorted(set(block) - set(_PLAN_MODEL_KEYS))
+    if unknown:
+        raise ValueError(f"plan_models: unknown keys {unknown}; known: {list(_PLAN_MODEL_KEYS)}")
+    per = block.get("per", "plan")
+    if per not in ("plan", "sample"):
+        raise ValueError(f"plan_models: per = {per!r}; 'plan' or 'sample' are allowed")
+    variants = block.get("variants")
+    if not isinstance(variants, (list, tuple)) or len(variants) < 1:
+        raise ValueError("plan_models: variants is a non-empty list of mjcf.vary_model keyword mappings ({} is the env's model)")
+    models = []
+    for v, entry in enumerate(variants):
+        try:
+            models.append(sim_model_settings({} if entry is None else entry, model))
+        except ValueError as e:
+            raise ValueError(f"plan_models: variant {v}: {str(e).replace('sim_model: ', '').replace('sim_model ', 'it ')}") from None
+    rows = int(Nsample) + 1 if per == "sample" else int(n_plans)
+    index = _lib.plan_model_index(block.get("model_of"), len(models), rows, per)
+    return models, index, per
+
+
+def _plan_models_kw(config_dict, dial_config, env, n_plans: int) -> Dict[str, Any]:
+    """The MBDPI keywords of the YAML's optional plan_models block; {} when it is absent (nothing is bound)."""
+    block = config_dict.get("plan_models")
+    if block is None:
+        return {}
+    models, index, per = plan_models_settings(block, env.sys.model, n_plans, dial_config.Nsample)
+    print(f"planner models: {len(models)} variants per {per}, model_of = {index.tolist() if index.size <= 32 else str(index[:32].tolist()) + ' ...'}")
+    return dict(models=models, model_of=index, model_per=per)
+
+
 def _positive_int(v: str) -> int:
     n = int(v)
     if n < 1:
@@ -335,12 +409,14 @@ def main(argv=None):
     if args.n_steps is not None:
         dial_config.n_steps = args.n_steps
     env_params = _env_params(parser, args, env)
+    model_kw = _plan_models_kw(config_dict, dial_config, env, args.n_envs)
     if args.n_envs > 1:
+        extra = dict(model_kw=model_kw) if model_kw else {}   # (absent block: the calls are the ones of before)
         if env_params:
-            return main_batched(dial_config, env, args.n_envs, env_params=env_params)
-        return main_batched(dial_config, env, args.n_envs)
+            return main_batched(dial_config, env, args.n_envs, env_params=env_params, **extra)
+        return main_batched(dial_config, env, args.n_envs, **extra)
     print("Creating environment")
-    mbdpi = MBDPI(dial_config, env)
+    mbdpi = MBDPI(dial_config, env, **model_kw)
     rng = _generator(dial_config.seed, mbdpi.device)
     state = env.reset(rng)
     Y0 = torch.zeros((dial_config.Hnode + 1, mbdpi.nu), dtype=torch.float32, device=mbdpi.device)
@@ -415,12 +491,13 @@ def batched_loop(mbdpi: "MBDPI", env, states, n_steps: int, eps_fn=None, on_tick
     return rollouts, infos, tick_ms
 
 
-def main_batched(dial_config, env, n_envs: int, env_params=None):
+def main_batched(dial_config, env, n_envs: int, env_params=None, model_kw=None):
     """``--n-envs M``: M closed loops from env.reset, each with its own plan noise, planned in one launch per annealing iteration.
-    env_params: {name: [M values]} -- per-loop task parameters of a custom environment (``--env-param``)."""
+    env_params: {name: [M values]} -- per-loop task parameters of a custom environment (``--env-param``).
+    model_kw: MBDPI's models / model_of / model_per keywords (the YAML's plan_models block)."""
     print(f"Creating environment ({n_envs} closed loops, planned together)")
     rows = env.plan_params(**env_params) if env_params else None
-    mbdpi = MBDPI(dial_config, env, n_plans=n_envs)
+    mbdpi = MBDPI(dial_config, env, n_plans=n_envs, **(model_kw or {}))
     states = [env.reset() for _ in range(n_envs)]
 
     def on_tick(t, sts, ms):

@@ -26,6 +26,7 @@
 #include "plant_plugin.h"
 #include "plant_dist_kernel.h"
 #include "plant_var_kernel.h"
+#include "plan_var_kernel.h"
 #include "plugin_ops.h"
 
 // the kernels are compiled in their own translation units, one per robot family (kern_family.hip, built in parallel)
@@ -361,6 +362,11 @@ struct dial_ctx {
   void* plant_models = nullptr;            // per-plant model constants (dial_set_plant_models), context-owned: V blocks of constants,
   int32_t* plant_model_of = nullptr;       // (sizeof(CModel<D>) + 15) / 16 * 16 bytes apart, and the index int32[M]; nullptr: the context's own model
   int plant_models_V = 0, plant_models_M = 0;
+  const dial_plugin_plan_var* plug_plan_var = nullptr;       // inst 7: the plugin's per-model rollout kernel, nullptr: built without one
+  void* plan_models = nullptr;             // planner models (dial_set_plan_models), context-owned: V blocks of constants as above and
+  int32_t* plan_model_of = nullptr;        // the index int32[plan_models_rows]; nullptr: every rollout runs the context's own model
+  int plan_models_V = 0, plan_models_rows = 0, plan_models_mode = 0;
+  dial_plan_var_launch_fn plan_launch = nullptr;   // the kernel's launch function, looked up when the models were bound
   std::vector<float> user_params;          // inst 7: the current user parameters and reference-table binding, as dial_create_plugin /
   const float* user_table = nullptr;       // dial_set_user_params / dial_set_user_table last set them (dial_set_plant_models writes
   int user_table_rows = 0, user_table_cols = 0, user_table_row0 = 0, user_table_mode = 0;   // them into every block it builds)
@@ -479,7 +485,7 @@ void dial_destroy(dial_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   void* ptrs[] = {ctx->dcm, ctx->dtask, ctx->dcfg, ctx->prof, ctx->next, ctx->relay_buf, ctx->relay_flag, ctx->Y0s, ctx->rewss, ctx->rews, ctx->qss,
                   ctx->qdss,   ctx->xss,   ctx->weights, ctx->partial, ctx->ovf, ctx->slice_buf, ctx->slice_flag, ctx->work_stat,
-                  ctx->plant_models, ctx->plant_model_of};
+                  ctx->plant_models, ctx->plant_model_of, ctx->plan_models, ctx->plan_model_of};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -561,8 +567,13 @@ int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task*
   if (int rc = plugin_table(h, plugin_path, DIAL_PLUGIN_PLANT_VAR_SYMBOL, "plant-models table", DIAL_PLUGIN_PLANT_VAR_VERSION, &plv)) return rc;
   if (plv && (!pla || plv->cmodel_bytes != ops->cmodel_bytes || plv->nq != model->nq || plv->nv != model->nv || plv->nu != model->nu || !plv->launch))
     return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's plant-models table was built against another version of the library (ABI mismatch; rebuild it)");
+  // the per-model rollout kernel's table: a seventh symbol, exported only by a plugin built with build_plugin(plan_models=True)
+  const dial_plugin_plan_var* pnv;
+  if (int rc = plugin_table(h, plugin_path, DIAL_PLUGIN_PLAN_VAR_SYMBOL, "plan-models table", DIAL_PLUGIN_PLAN_VAR_VERSION, &pnv)) return rc;
+  if (pnv && (pnv->cmodel_bytes != ops->cmodel_bytes || pnv->nq != model->nq || pnv->nv != model->nv || pnv->nu != model->nu || !pnv->launch))
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's plan-models table was built against another version of the library (ABI mismatch; rebuild it)");
   const int rc = create_impl(out, model, task, cfg, device, -1, opts, ops, params, n_params);
-  if (rc == DIAL_OK) { (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; (*out)->plug_plant = pla; (*out)->plug_plant_dist = pld; (*out)->plug_plant_var = plv; }
+  if (rc == DIAL_OK) { (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; (*out)->plug_plant = pla; (*out)->plug_plant_dist = pld; (*out)->plug_plant_var = plv; (*out)->plug_plan_var = pnv; }
   return rc;
 }
 
@@ -586,6 +597,9 @@ int dial_set_user_params(dial_ctx* ctx, const float* params, int n) {
   if (ctx->plant_models)
     return fail(ctx, DIAL_ERR_ARG, "dial_set_user_params: plant models are bound, and their constants carry a copy of the parameters; unbind first "
                                    "(dial_set_plant_models(ctx, NULL, 0, NULL, 0)), then bind again");
+  if (ctx->plan_models)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_user_params: plan models are bound, and their constants carry a copy of the parameters; unbind first "
+                                   "(dial_set_plan_models(ctx, NULL, 0, NULL, 0, 0)), then bind again");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->plug->set_params(ctx->plug_cm.data(), params, n);
   ctx->user_params.assign(params, params + n);
@@ -610,6 +624,9 @@ int dial_set_user_table(dial_ctx* ctx, const float* table, int rows, int cols, i
   if (ctx->plant_models)
     return fail(ctx, DIAL_ERR_ARG, "dial_set_user_table: plant models are bound, and their constants carry a copy of the table's binding; unbind first "
                                    "(dial_set_plant_models(ctx, NULL, 0, NULL, 0)), then bind again");
+  if (ctx->plan_models)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_user_table: plan models are bound, and their constants carry a copy of the table's binding; unbind first "
+                                   "(dial_set_plan_models(ctx, NULL, 0, NULL, 0, 0)), then bind again");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->plug_table->set_table(ctx->plug_cm.data(), table, rows, cols, row0, mode);
   ctx->user_table = table; ctx->user_table_rows = rows; ctx->user_table_cols = cols; ctx->user_table_row0 = row0; ctx->user_table_mode = mode;
@@ -1080,6 +1097,40 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
     e1 = ctx->events[ctx->events_used].second;
     ctx->events_used++;
     HIP_TRY(ctx, hipEventRecord(e0, st));
+  }
+  // planner models are bound (dial_set_plan_models): the kernel of plan_var_kernel.h -- one wavefront per rollout on a plain grid,
+  // every rollout on its own block of constants -- instead of every path below (none of them can change constants inside a launch)
+  if (ctx->plan_models) {
+    // (a refused launch records no time: its event pair goes back)
+    const auto refuse = [&](int code, const std::string& msg) { if (ctx->timing) ctx->events_used--; return fail(ctx, code, msg); };
+    if (ctx->trace)
+      return refuse(DIAL_ERR_UNSUPPORTED, "rollout launch: plan models are bound and so is a state trace; the per-model rollout kernel has no trace "
+                                             "instantiation (unbind one: dial_set_state_trace(ctx, NULL, 0) or dial_set_plan_models(ctx, NULL, 0, NULL, 0, 0))");
+    if (ctx->plan_models_mode == DIAL_PLAN_MODELS_PER_PLAN) {
+      const int plans = io_in.plan_rollouts ? B / io_in.plan_rollouts : 1;
+      if (plans > ctx->plan_models_rows)
+        return refuse(DIAL_ERR_ARG, "rollout launch: M = " + std::to_string(plans) + " plans, but the bound plan models index " +
+                                       std::to_string(ctx->plan_models_rows) + " plans (dial_set_plan_models, DIAL_PLAN_MODELS_PER_PLAN)");
+    } else if (!io_in.plan_rollouts && B > ctx->plan_models_rows) {
+      return refuse(DIAL_ERR_ARG, "rollout launch: B = " + std::to_string(B) + " rollouts, but the bound plan models index " +
+                                     std::to_string(ctx->plan_models_rows) + " samples (dial_set_plan_models, DIAL_PLAN_MODELS_PER_SAMPLE)");
+    }
+    dial::RolloutIO io = io_in;
+    io.plan_params = ctx->plan_params;
+    io.con_cap = ctx->ovf ? ctx->con_cap : 0;
+    io.ovf = ctx->ovf;
+    io.ovf_words = ctx->ovf_words;
+    if (io.ovf && B > ctx->ovf_slots)
+      return refuse(DIAL_ERR_ARG, "rollout launch: more wavefronts than overflow areas (batch larger than the context's Nsample + 1)");
+    size_t lds = ctx->cm_bytes + (size_t)ctx->ws_words * sizeof(float);   // the staged constants + ONE workspace
+#ifdef DIAL_PROFILE
+    lds += 16 + 32 * sizeof(unsigned long long);
+#endif
+    ll[LF_WPB] = 1; ll[LF_BLOCKS] = B; ll[LF_CON_CAP] = io.con_cap;
+    HIP_TRY(ctx, ctx->plan_launch(lds, st, ctx->plan_models, (const dial_task*)ctx->dtask, (const dial_cfg*)ctx->dcfg, &io, B, ctx->ws_words,
+                                  ctx->plan_model_of, ctx->plan_models_mode == DIAL_PLAN_MODELS_PER_SAMPLE));
+    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(e1, st));
+    return DIAL_OK;
   }
   // batches beyond what the chip keeps resident: launch exactly the resident grid and let the wavefronts draw the
   // remaining rollouts from a queue (see rollout_kernel); the queue head starts behind the grid's own first rollouts
@@ -1817,6 +1868,36 @@ static std::string plant_model_refusal(const dial_ctx* ctx, const dial_model* mo
   return std::string();
 }
 
+// dial_set_plant_models / dial_set_plan_models: the V blocks of constants on the host, each model checked first (plant_model_refusal)
+static int model_blocks(dial_ctx* ctx, const dial_model* models, int V, const char* who, std::vector<char>& blocks) {
+  // the V blocks on the host: what dial_create uploads for each model, `stride` bytes apart (the kernels stage 16-byte words)
+  const size_t stride = (ctx->dcm_bytes + 15) / 16 * 16;
+  blocks.assign((size_t)V * stride, 0);
+  std::vector<dial_derived> dvs(1);
+  for (int v = 0; v < V; v++) {
+    const dial_model* mv = models + v;
+    const std::string no = plant_model_refusal(ctx, mv, &dvs[0]);
+    if (!no.empty()) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": model " + std::to_string(v) + " is rejected: " + no);
+    char* dst = blocks.data() + (size_t)v * stride;
+    if (ctx->plug) {   // the context's current parameters and reference table, through the functions that wrote them into plug_cm
+      ctx->plug->fill(dst, mv, &ctx->ht, &dvs[0], ctx->user_params.data(), (int)ctx->user_params.size());
+      if (ctx->plug_table && ctx->user_table)
+        ctx->plug_table->set_table(dst, ctx->user_table, ctx->user_table_rows, ctx->user_table_cols, ctx->user_table_row0, ctx->user_table_mode);
+    } else {
+      switch (ctx->inst) {
+        case 0: plant_model_block<DimsMax>(dst, mv, &ctx->ht, &dvs[0]); break;
+        case 1: plant_model_block<DimsGo2>(dst, mv, &ctx->ht, &dvs[0]); break;
+        case 2: plant_model_block<DimsH1>(dst, mv, &ctx->ht, &dvs[0]); break;
+        case 3: plant_model_block<DimsH1Loco>(dst, mv, &ctx->ht, &dvs[0]); break;
+        case 4: plant_model_block<DimsAllegro>(dst, mv, &ctx->ht, &dvs[0]); break;
+        case 5: plant_model_block<DimsGo2Crate>(dst, mv, &ctx->ht, &dvs[0]); break;
+        default: plant_model_block<DimsH1PushCrate>(dst, mv, &ctx->ht, &dvs[0]); break;   // (6: the caller has checked the range)
+      }
+    }
+  }
+  return DIAL_OK;
+}
+
 #endif
 
 int dial_set_plant_models(dial_ctx* ctx, const dial_model* models, int V, const int32_t* model_of, int M) {
@@ -1847,31 +1928,8 @@ int dial_set_plant_models(dial_ctx* ctx, const dial_model* models, int V, const 
   std::string why;
   if (!plant_var_launch_of(ctx, why)) return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_set_plant_models: " + why);
 #ifndef DIAL_IEEE_BUILD
-  // the V blocks on the host: what dial_create uploads for each model, `stride` bytes apart (the kernels stage 16-byte words)
-  const size_t stride = (ctx->dcm_bytes + 15) / 16 * 16;
-  std::vector<char> blocks((size_t)V * stride, 0);
-  std::vector<dial_derived> dvs(1);
-  for (int v = 0; v < V; v++) {
-    const dial_model* mv = models + v;
-    const std::string no = plant_model_refusal(ctx, mv, &dvs[0]);
-    if (!no.empty()) return fail(ctx, DIAL_ERR_ARG, "dial_set_plant_models: model " + std::to_string(v) + " is rejected: " + no);
-    char* dst = blocks.data() + (size_t)v * stride;
-    if (ctx->plug) {   // the context's current parameters and reference table, through the functions that wrote them into plug_cm
-      ctx->plug->fill(dst, mv, &ctx->ht, &dvs[0], ctx->user_params.data(), (int)ctx->user_params.size());
-      if (ctx->plug_table && ctx->user_table)
-        ctx->plug_table->set_table(dst, ctx->user_table, ctx->user_table_rows, ctx->user_table_cols, ctx->user_table_row0, ctx->user_table_mode);
-    } else {
-      switch (ctx->inst) {
-        case 0: plant_model_block<DimsMax>(dst, mv, &ctx->ht, &dvs[0]); break;
-        case 1: plant_model_block<DimsGo2>(dst, mv, &ctx->ht, &dvs[0]); break;
-        case 2: plant_model_block<DimsH1>(dst, mv, &ctx->ht, &dvs[0]); break;
-        case 3: plant_model_block<DimsH1Loco>(dst, mv, &ctx->ht, &dvs[0]); break;
-        case 4: plant_model_block<DimsAllegro>(dst, mv, &ctx->ht, &dvs[0]); break;
-        case 5: plant_model_block<DimsGo2Crate>(dst, mv, &ctx->ht, &dvs[0]); break;
-        default: plant_model_block<DimsH1PushCrate>(dst, mv, &ctx->ht, &dvs[0]); break;   // (6: plant_var_launch_of has checked the range)
-      }
-    }
-  }
+  std::vector<char> blocks;
+  if (int rc = model_blocks(ctx, models, V, "dial_set_plant_models", blocks)) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   void* dblocks = nullptr;
   int32_t* dindex = nullptr;
@@ -1891,6 +1949,139 @@ int dial_set_plant_models(dial_ctx* ctx, const dial_model* models, int V, const 
   ctx->plant_model_of = dindex;
   ctx->plant_models_V = V;
   ctx->plant_models_M = M;
+#endif
+  return DIAL_OK;
+}
+
+#ifndef DIAL_IEEE_BUILD
+// libdialplanvar.so (plan_var_family.hip): the rollout kernels with per-plan / per-sample model constants, looked up the first time
+// planner models are bound
+struct PlanVarLib {
+  const dial_plan_var_ops* ops = nullptr;
+  std::string err;
+};
+static PlanVarLib plan_var_load() {
+  PlanVarLib r;
+  Dl_info info{};
+  std::string dir = ".";
+  if (dladdr((const void*)&plan_var_load, &info) && info.dli_fname) {
+    dir = info.dli_fname;
+    const size_t slash = dir.rfind('/');
+    dir = slash == std::string::npos ? "." : dir.substr(0, slash);
+  }
+  const std::string path = dir + "/libdialplanvar.so";
+  void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);   // (never dlclose'd: the runtime holds its code objects)
+  if (!h) { r.err = "cannot load " + path + " (build it: dial_mpc_amd._lib.build()): " + dlerror(); return r; }
+  dial_plan_var_entry entry = (dial_plan_var_entry)dlsym(h, DIAL_PLAN_VAR_SYMBOL);
+  const dial_plan_var_ops* o = entry ? entry() : nullptr;
+  if (!o) r.err = path + " does not export " DIAL_PLAN_VAR_SYMBOL;
+  else if (o->abi_version != DIAL_PLAN_VAR_ABI_VERSION || o->sizeof_model != sizeof(dial_model) || o->sizeof_task != sizeof(dial_task) ||
+           o->sizeof_cfg != sizeof(dial_cfg) || o->sizeof_io != sizeof(dial::RolloutIO))
+    r.err = path + " was built against another version of the library (rebuild it)";
+  else r.ops = o;
+  return r;
+}
+static const PlanVarLib& plan_var_lib() {
+  static const PlanVarLib lib = plan_var_load();   // (once per process, thread-safe initialisation)
+  return lib;
+}
+#endif
+
+// The per-model rollout kernel's launch function of a context: the plugin's seventh table, or libdialplanvar.so's entry of the
+// context's instantiation.  nullptr with the reason in `why` (DIAL_ERR_UNSUPPORTED).
+static dial_plan_var_launch_fn plan_var_launch_of(dial_ctx* ctx, std::string& why) {
+#ifdef DIAL_IEEE_BUILD
+  (void)ctx;
+  why = "the IEEE measurement build carries no per-model rollout kernel (use the product library)";
+  return nullptr;
+#else
+  if (ctx->plug) {
+    if (!ctx->plug_plan_var) {
+      why = "the context's task plugin does not export " DIAL_PLUGIN_PLAN_VAR_SYMBOL " (build it with build_plugin(plan_models=True); "
+            "CustomEnv.plugin_path(plan_models=True) does)";
+      return nullptr;
+    }
+    return ctx->plug_plan_var->launch;
+  }
+  const PlanVarLib& lib = plan_var_lib();
+  if (!lib.ops) { why = lib.err; return nullptr; }
+  if (ctx->inst < 0 || ctx->inst >= DIAL_PLAN_VAR_INSTS || lib.ops->cmodel_bytes[ctx->inst] != ctx->dcm_bytes) {
+    why = "libdialplanvar.so does not match this library's constants (rebuild both)";
+    return nullptr;
+  }
+  if (!lib.ops->launch[ctx->inst]) {
+    why = "libdialplanvar.so carries no per-model rollout kernel for kernel instantiation " + std::to_string(ctx->inst);
+    return nullptr;
+  }
+  return lib.ops->launch[ctx->inst];
+#endif
+}
+
+int dial_set_plan_models(dial_ctx* ctx, const dial_model* models, int V, const int32_t* model_of, int rows, int mode) {
+  if (!ctx) return fail(nullptr, DIAL_ERR_ARG, "dial_set_plan_models: null context");
+  if (!models && !model_of && V == 0 && rows == 0 && mode == 0) {   // unbind
+    if (ctx->plan_models) {
+      HIP_TRY(ctx, hipSetDevice(ctx->device));
+      HIP_TRY(ctx, hipDeviceSynchronize());   // (launches in flight read the blocks)
+      (void)hipFree(ctx->plan_models);
+      (void)hipFree(ctx->plan_model_of);
+    }
+    ctx->plan_models = nullptr;
+    ctx->plan_model_of = nullptr;
+    ctx->plan_models_V = ctx->plan_models_rows = ctx->plan_models_mode = 0;
+    ctx->plan_launch = nullptr;
+    return DIAL_OK;
+  }
+  if (V < 1 || V > DIAL_MAX_PLAN_MODELS)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: V = " + std::to_string(V) + " is outside 1 .. DIAL_MAX_PLAN_MODELS");
+  if (rows < 1) return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: rows = " + std::to_string(rows) + " must be >= 1");
+  if (!models || !model_of)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: a null pointer with V = " + std::to_string(V) + ", rows = " + std::to_string(rows) +
+                                   " (NULL, 0, NULL, 0, 0 unbinds)");
+  if (mode != DIAL_PLAN_MODELS_PER_PLAN && mode != DIAL_PLAN_MODELS_PER_SAMPLE)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: unknown mode " + std::to_string(mode) +
+                                   " (DIAL_PLAN_MODELS_PER_PLAN or DIAL_PLAN_MODELS_PER_SAMPLE)");
+  if (!ctx->has_cfg) return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: context was created without a dial_cfg (it launches no rollouts)");
+  if (ctx->B_cap < ctx->hc.Nsample + 1)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: the context is sharded (n_local_cap < Nsample)");
+  if (mode == DIAL_PLAN_MODELS_PER_PLAN && rows > ctx->plan_cap)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: rows = " + std::to_string(rows) + " exceeds the context's plan capacity " +
+                                   std::to_string(ctx->plan_cap) + " (dial_options.plan_cap; DIAL_PLAN_MODELS_PER_PLAN has one row per plan)");
+  if (mode == DIAL_PLAN_MODELS_PER_SAMPLE && rows != ctx->hc.Nsample + 1)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: rows = " + std::to_string(rows) + ", DIAL_PLAN_MODELS_PER_SAMPLE needs Nsample + 1 = " +
+                                   std::to_string(ctx->hc.Nsample + 1) + " (one row per noisy sample and the mean trajectory's)");
+  for (int r = 0; r < rows; r++)
+    if (model_of[r] < 0 || model_of[r] >= V)
+      return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: model_of[" + std::to_string(r) + "] = " + std::to_string(model_of[r]) + " is outside 0 .. V - 1 = " +
+                                     std::to_string(V - 1));
+  std::string why;
+  dial_plan_var_launch_fn launch = plan_var_launch_of(ctx, why);
+  if (!launch) return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_set_plan_models: " + why);
+#ifndef DIAL_IEEE_BUILD
+  // (the context's own timestep is the one plant_model_refusal compares with: a planner model keeps it)
+  std::vector<char> blocks;
+  if (int rc = model_blocks(ctx, models, V, "dial_set_plan_models", blocks)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  void* dblocks = nullptr;
+  int32_t* dindex = nullptr;
+  hipError_t e = hipMalloc(&dblocks, blocks.size());
+  if (e == hipSuccess) e = hipMalloc((void**)&dindex, (size_t)rows * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemcpy(dblocks, blocks.data(), blocks.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dindex, model_of, (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // (launches in flight read the previous binding's blocks)
+  if (e != hipSuccess) {
+    if (dblocks) (void)hipFree(dblocks);
+    if (dindex) (void)hipFree(dindex);
+    return fail(ctx, DIAL_ERR_HIP, std::string("dial_set_plan_models: uploading the constants failed: ") + hipGetErrorString(e));
+  }
+  if (ctx->plan_models) (void)hipFree(ctx->plan_models);
+  if (ctx->plan_model_of) (void)hipFree(ctx->plan_model_of);
+  ctx->plan_models = dblocks;
+  ctx->plan_model_of = dindex;
+  ctx->plan_models_V = V;
+  ctx->plan_models_rows = rows;
+  ctx->plan_models_mode = mode;
+  ctx->plan_launch = launch;
 #endif
   return DIAL_OK;
 }

@@ -13,6 +13,8 @@
 // (plant_dist_kernel.h: velocity kicks and actuator errors, dial_set_plant_disturbance) and a fifth table, dial_plugin_plant_dist.
 // -DDIAL_PLUGIN_PLANT_VAR=1 next to DIAL_PLUGIN_PLANT (build_plugin(plant_models=True)) adds plant_var_kernel<DimsPlugin>
 // (plant_var_kernel.h: per-plant model constants, dial_set_plant_models) and a sixth table, dial_plugin_plant_var.
+// -DDIAL_PLUGIN_PLAN_VAR=1 (build_plugin(plan_models=True), with or without a plant) adds rollout_var_kernel<DimsPlugin>
+// (plan_var_kernel.h: per-plan / per-sample planner models, dial_set_plan_models) and a seventh table, dial_plugin_plan_var.
 #include "plugin_ops.h"
 #ifndef DIAL_PLUGIN_PLANT
 #define DIAL_PLUGIN_PLANT 0
@@ -37,6 +39,12 @@
 #endif
 #if DIAL_PLUGIN_PLANT_VAR
 #include "plant_var_kernel.h"
+#endif
+#ifndef DIAL_PLUGIN_PLAN_VAR
+#define DIAL_PLUGIN_PLAN_VAR 0
+#endif
+#if DIAL_PLUGIN_PLAN_VAR
+#include "plan_var_kernel.h"
 #endif
 #include "dial_plugin_dims.h"
 #include "dial_user_reward.hip"
@@ -106,5 +114,14 @@ template __global__ void plant_var_kernel<DimsPlugin>(const CModel<DimsPlugin>*,
 
 extern "C" __attribute__((visibility("default"))) const dial_plugin_plant_var* dial_plugin_plant_var_v1(void) {
   return PluginPlantVar<DimsPlugin>::table();
+}
+#endif
+
+#if DIAL_PLUGIN_PLAN_VAR
+template __global__ void rollout_var_kernel<DimsPlugin>(const CModel<DimsPlugin>*, const dial_task*, const dial_cfg*, dial::RolloutIO, int, int,
+                                                         const int32_t*, int);
+
+extern "C" __attribute__((visibility("default"))) const dial_plugin_plan_var* dial_plugin_plan_var_v1(void) {
+  return PluginPlanVar<DimsPlugin>::table();
 }
 #endif

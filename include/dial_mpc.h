@@ -74,6 +74,9 @@ extern "C" {
 #define DIAL_PLANT_MAX_EVENTS 16
 #define DIAL_PLANT_DIST_ROW(nu, nv, E) (2 * (nu) + (E) * (2 + (nv)))
 #define DIAL_MAX_PLANT_MODELS 1024 /* dial_set_plant_models: distinct plant models of one binding */
+#define DIAL_MAX_PLAN_MODELS 1024 /* dial_set_plan_models: distinct planner models of one binding */
+#define DIAL_PLAN_MODELS_PER_PLAN 0 /* model_of[rows <= plan_cap]: plan g runs models[model_of[g]]; one-plan launches read row 0 */
+#define DIAL_PLAN_MODELS_PER_SAMPLE 1 /* model_of[rows == Nsample + 1]: local rollout nl of EVERY plan runs models[model_of[nl]]; row Nsample is the mean trajectory's */
 
 /* joint types (MuJoCo numbering) */
 #define DIAL_JNT_FREE 0
@@ -668,6 +671,38 @@ int dial_set_plant_disturbance(dial_ctx* ctx, const float* dist, int M, int n_ev
  * stale, on a task plugin without the table, and in the IEEE measurement build.  dial_plant_step fails with DIAL_ERR_ARG when its
  * M differs from the bound M. */
 int dial_set_plant_models(dial_ctx* ctx, const dial_model* models, int V, const int32_t* model_of, int M);
+/* Planner model ensembles: per-plan or per-sample rollout models.  models:[V] and model_of:[rows] are HOST arrays,
+ * 1 <= V <= DIAL_MAX_PLAN_MODELS, 0 <= model_of[r] < V.  The library COPIES them: it builds V blocks of kernel constants -- what
+ * dial_create builds from a model, with the context's task and options; on a task-plugin context with the context's current user
+ * parameters and reference-table binding -- and uploads them, with the index, into buffers the context owns (dial_destroy and a
+ * re-bind free them).  mode:
+ *   DIAL_PLAN_MODELS_PER_PLAN    1 <= rows <= the context's plan capacity (dial_options.plan_cap): every rollout of plan g of a grouped
+ *                                launch runs models[model_of[g]]; one-plan launches (dial_rollout, dial_reverse_once*) read row 0.
+ *   DIAL_PLAN_MODELS_PER_SAMPLE  rows == Nsample + 1: rollout nl of EVERY plan runs models[model_of[nl]], row Nsample is the mean
+ *                                trajectory's (domain-randomised sampling); dial_rollout's rollout n reads row n.
+ * While bound, dial_rollout, dial_reverse_once[_rng] and dial_reverse_once_batch[_rng] launch the kernel of csrc/plan_var_kernel.h
+ * (in libdialplanvar.so next to this library; on a task-plugin context the plugin's own, build_plugin(plan_models=True), behind
+ * the optional table dial_plugin_plan_var_v1): one wavefront per rollout on a plain grid, the same per-rollout program as every
+ * other rollout kernel on the rollout's own block of constants.  A rollout of such a launch equals, bit for bit, the same rollout
+ * of a context created from its model.  The softmax, weighted sums and shift are untouched, dial_set_timing keeps working, and
+ * per-plan task parameters (dial_set_plan_params) still apply.  dial_env_step*, dial_env_reset* and dial_plant_step IGNORE the
+ * binding: they run the context's own model (the plant has dial_set_plant_models).
+ * A model is accepted exactly when dial_set_plant_models would accept it for this context; its timestep must equal the context's
+ * own.  What may differ is every float (masses, inertias, centres of mass, friction, damping, armature, friction loss, ...), not
+ * the structure or the geometry's layout.
+ * (NULL, 0, NULL, 0, 0) unbinds: the launches take the paths they took before.  A failed call leaves the previous binding in
+ * place.  While models are bound, dial_set_user_params and dial_set_user_table fail with DIAL_ERR_ARG (unbind first: the blocks
+ * carry a copy of both).  Synchronises the device.
+ * Fails with DIAL_ERR_ARG and a message that starts with "dial_set_plan_models: " on a null context, V outside
+ * 1 .. DIAL_MAX_PLAN_MODELS, rows < 1, a null pointer with non-zero counts, an unknown mode, per-plan rows > plan_cap, per-sample
+ * rows != Nsample + 1, an index outside 0 .. V - 1, a rejected model (the message names its index and the reason), a sharded
+ * context (n_local_cap < Nsample) or one created without a dial_cfg; with DIAL_ERR_UNSUPPORTED when libdialplanvar.so is missing
+ * or stale or has no kernel for the context's family, on a task plugin without the table, and in the IEEE measurement build.
+ * A launch fails with DIAL_ERR_ARG when it groups more plans than the per-plan index has rows or when a dial_rollout has more
+ * rollouts than the per-sample index has rows, and with DIAL_ERR_UNSUPPORTED while a state trace is bound (dial_set_state_trace:
+ * the kernel has no trace instantiation).  Go2 batches above 2304 rollouts run this one-rollout-per-wavefront kernel too, not the
+ * pair kernel. */
+int dial_set_plan_models(dial_ctx* ctx, const dial_model* models, int V, const int32_t* model_of, int rows, int mode);
 
 /* ABI self-description used by tests: sizeof of the three structs. */
 int dial_abi_sizes(int* model_bytes, int* task_bytes, int* cfg_bytes);
