@@ -76,6 +76,7 @@ def build(force: bool = False, verbose: bool = False, ieee: bool = False) -> str
         build_plant_dist(force=force, verbose=verbose)
         build_plant_var(force=force, verbose=verbose)
         build_plan_var(force=force, verbose=verbose)
+        build_plan_ens(force=force, verbose=verbose)
     return _build_lib(IEEE_LIB_PATH if ieee else LIB_PATH, [(os.path.join(_CSRC, "dial_hip.hip"), [], "dial_hip.o")] +
                       [(os.path.join(_CSRC, "kern_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []), f"kern_family_{k}.o")
                        for k in range(N_FAMILIES)], force, verbose, ieee)
@@ -127,6 +128,19 @@ def build_plan_var(force: bool = False, verbose: bool = False) -> str:
     models are bound."""
     return _build_lib(PLAN_VAR_LIB_PATH, [(os.path.join(_CSRC, "plan_var_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []),
                                            f"plan_var_family_{k}.o") for k in range(N_PLANT_FAMILIES)], force, verbose, False)
+
+
+PLAN_ENS_LIB_PATH = os.path.join(_CSRC, "libdialplanens.so")
+
+
+def build_plan_ens(force: bool = False, verbose: bool = False) -> str:
+    """libdialplanens.so: the ensemble rollout kernel (csrc/plan_ens_kernel.h: dial_set_plan_ensemble) once per robot family
+    (plan_ens_family.hip -DDIAL_FAMILY=k, build_plant's flags) and the aggregation kernel in a unit of its own
+    (plan_ens_aggregate.hip), a library of its own so that the code objects of every other library stay as shipped.  libdialhip.so
+    loads it from its own directory the first time an ensemble is bound."""
+    return _build_lib(PLAN_ENS_LIB_PATH, [(os.path.join(_CSRC, "plan_ens_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []),
+                                           f"plan_ens_family_{k}.o") for k in range(N_PLANT_FAMILIES)] +
+                      [(os.path.join(_CSRC, "plan_ens_aggregate.hip"), [], "plan_ens_aggregate.o")], force, verbose, False)
 
 
 def _build_lib(out: str, units, force: bool, verbose: bool, ieee: bool) -> str:
@@ -269,6 +283,12 @@ def load(path: Optional[str] = None):
     except AttributeError:
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack planner models)
             raise
+    try:
+        lib.dial_set_plan_ensemble.argtypes = [vp, vp, ci, vp, ci, ci, ci, ctypes.c_float]
+        lib.dial_get_ensemble_rewards.argtypes = [vp, fp, ci, vp]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack plan ensembles)
+            raise
     lib.dial_env_reset.argtypes = [vp, fp, fp, fp, fp, fp, vp]
     lib.dial_env_reset_batch.argtypes = [vp, fp, fp, fp, fp, fp, ci, vp]
     lib.dial_status.argtypes = [vp]
@@ -297,7 +317,7 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
             "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch",
             "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params", "dial_plant_step", "dial_user_control",
             "dial_set_user_table", "dial_set_plant_disturbance", "dial_set_plant_models",
-            "dial_set_plan_models")
+            "dial_set_plan_models", "dial_set_plan_ensemble", "dial_get_ensemble_rewards")
 
 # dial_plant_step flags (include/dial_mpc.h)
 PLANT_CTRL, PLANT_PD, PLANT_HOLD_FIRST = (_abi.MACROS[k] for k in ("DIAL_PLANT_CTRL", "DIAL_PLANT_PD", "DIAL_PLANT_HOLD_FIRST"))
@@ -360,6 +380,39 @@ def plan_model_index(model_of, V: int, rows: int, per: str = "plan") -> np.ndarr
                          f"{'one per plan' if per == 'plan' else 'Nsample + 1, the mean trajectory last'}); got shape {a.shape}, dtype {a.dtype}")
     if a.min() < 0 or a.max() >= V:
         raise ValueError(f"plan models: model_of holds indices outside 0 .. V - 1 = {V - 1}")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+MAX_ENSEMBLE = _abi.MACROS["DIAL_MAX_ENSEMBLE"]   # hypotheses per plan of one ensemble (dial_set_plan_ensemble)
+ENSEMBLE_AGGREGATES = {"mean": _abi.MACROS["DIAL_ENSEMBLE_MEAN"], "min": _abi.MACROS["DIAL_ENSEMBLE_MIN"], "cvar": _abi.MACROS["DIAL_ENSEMBLE_CVAR"]}
+
+
+def plan_ensemble_index(hyp, V: int, rows: int, R: Optional[int] = None) -> np.ndarray:
+    """The hypotheses dial_set_plan_ensemble takes: contiguous int32 [rows, R] with 0 <= hyp[g, r] < V -- plan g rolls every
+    candidate out under models[hyp[g, 0 .. R-1]], hypothesis 0 its nominal model.  hyp None: every plan gets all V models in order
+    (R = V).  A flat list of R indices is shared by all plans.  Raises ValueError on another shape, a non-integer, an index out of
+    range, R outside 1 .. DIAL_MAX_ENSEMBLE or rows outside 1 .. DIAL_MAX_PLANS."""
+    V, rows = int(V), int(rows)
+    if not 1 <= V <= MAX_PLAN_MODELS:
+        raise ValueError(f"plan ensemble: {V} models; 1 .. DIAL_MAX_PLAN_MODELS = {MAX_PLAN_MODELS} are allowed")
+    if not 1 <= rows <= _abi.MACROS["DIAL_MAX_PLANS"]:
+        raise ValueError(f"plan ensemble: {rows} rows; 1 .. DIAL_MAX_PLANS = {_abi.MACROS['DIAL_MAX_PLANS']} are allowed (one per plan)")
+    if hyp is None:
+        if R is not None and int(R) != V:
+            raise ValueError(f"plan ensemble: R = {R} without hypotheses; the default is all V = {V} models in order (R = V)")
+        a = np.tile(np.arange(V, dtype=np.int32), (rows, 1))
+    else:
+        a = np.asarray(hyp)
+        if a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"plan ensemble: hyp is a non-empty integer list [R] or [rows][R]; got shape {a.shape}, dtype {a.dtype}")
+        if a.ndim == 1:
+            a = np.tile(a, (rows, 1))
+        if a.ndim != 2 or a.shape[0] != rows or (R is not None and a.shape[1] != int(R)):
+            raise ValueError(f"plan ensemble: hyp is [R] or [rows = {rows}][R{'' if R is None else f' = {int(R)}'}]; got shape {a.shape}")
+        if a.min() < 0 or a.max() >= V:
+            raise ValueError(f"plan ensemble: hyp holds indices outside 0 .. V - 1 = {V - 1}")
+    if not 1 <= a.shape[1] <= MAX_ENSEMBLE:
+        raise ValueError(f"plan ensemble: R = {a.shape[1]} hypotheses per plan; 1 .. DIAL_MAX_ENSEMBLE = {MAX_ENSEMBLE} are allowed")
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
@@ -692,6 +745,44 @@ class Context:
         self._check(self.lib.dial_set_plan_models(self.h, ctypes.addressof(arr), len(models), index.ctypes.data, int(index.size),
                                                   PLAN_MODEL_MODES[per]), "dial_set_plan_models")
         return index
+
+    def set_plan_ensemble(self, models, hyp=None, aggregate: str = "mean", alpha: float = 1.0):
+        """Bind a model ensemble (dial_set_plan_ensemble): `models` a list of V compiled model dicts or DialModel structs (variants of
+        this context's model, as set_plan_models takes them), `hyp` [rows <= plan_cap][R] indices into it (a flat [R] list: shared by
+        every plan of the context's plan capacity; None: all V models in order for every plan).  While bound, reverse_once* (row 0)
+        and reverse_once_batch* (M <= rows plans) roll every candidate out under all R hypotheses of its plan and run the softmax
+        on the per-candidate aggregate: "mean", "min" or "cvar" (the mean of the ceil(alpha R) worst; alpha in (0, 1]).  qbar / qdbar /
+        xbar are the weighted means of the trajectories under hypothesis 0, the plan's nominal model.  rollout, env_step*, env_reset*
+        and plant_step ignore the binding.  models None unbinds.  Returns the hypotheses bound."""
+        if models is None:
+            self._check(self.lib.dial_set_plan_ensemble(self.h, None, 0, None, 0, 0, 0, 0.0), "dial_set_plan_ensemble")
+            self._ens_R = 0
+            return None
+        models = list(models)
+        if aggregate not in ENSEMBLE_AGGREGATES:
+            raise ValueError(f"plan ensemble: aggregate = {aggregate!r}; {sorted(ENSEMBLE_AGGREGATES)} are allowed")
+        if self.cfg is None:
+            raise ValueError("plan ensemble: the context was created without a dial_cfg (it launches no rollouts)")
+        a = None if hyp is None else np.asarray(hyp)
+        rows = a.shape[0] if a is not None and a.ndim == 2 else self.plan_cap
+        index = plan_ensemble_index(hyp, len(models), rows)
+        arr = (_abi.DialModel * len(models))()
+        for v, m in enumerate(models):
+            struct = m if isinstance(m, _abi.DialModel) else _abi.make_model(m)   # (kept alive across the copy)
+            ctypes.memmove(ctypes.addressof(arr[v]), ctypes.addressof(struct), ctypes.sizeof(_abi.DialModel))
+        self._check(self.lib.dial_set_plan_ensemble(self.h, ctypes.addressof(arr), len(models), index.ctypes.data, int(index.shape[0]),
+                                                    int(index.shape[1]), ENSEMBLE_AGGREGATES[aggregate], float(alpha)), "dial_set_plan_ensemble")
+        self._ens_R = int(index.shape[1])
+        return index
+
+    def ensemble_rewards(self, M: int):
+        """The raw per-hypothesis rewards [R, M, Nsample + 1] of the last robust iteration (dial_get_ensemble_rewards): row [r, g] holds
+        plan g's candidates under its hypothesis r, the mean trajectory's last."""
+        import torch
+        R = getattr(self, "_ens_R", 0)
+        out = torch.empty((max(R, 1), int(M), self.cfg.Nsample + 1), dtype=torch.float32, device=self.torch_device)
+        self._check(self.lib.dial_get_ensemble_rewards(self.h, _ptr(out), int(M), _stream()), "dial_get_ensemble_rewards")
+        return out
 
     # ---- K3
     def rollout(self, state, us, want_states: bool = True):

@@ -40,14 +40,16 @@ def softmax_update(weights, Y0s, sigma, mu_0t):
 class MBDPI:
     def __init__(self, args: DialConfig, env, device: Optional[int] = None, kernel_rng: bool = False,
                  force_sharded: bool = False, options: Optional[dict] = None, n_plans: int = 1,
-                 models=None, model_of=None, model_per: str = "plan"):
+                 models=None, model_of=None, model_per: str = "plan", ensemble: Optional[dict] = None):
         """kernel_rng=True: the noise is generated inside the rollout kernel (Philox keyed by args.seed and a call
         counter) instead of by torch.randn -- the production setting; parity runs pass `eps` explicitly.
         force_sharded (measurement hook): run the sharded code path, collectives included, on a 1-rank process group.
         options: `dial_options` fields for the context (launch-shape / measurement switches, include/dial_mpc.h).
         n_plans: plans one reverse_once_batch call may carry (the context's dial_options.plan_cap).
         models / model_of / model_per: planner models bound at creation (set_models); a custom environment's context is then created on
-        the plugin that carries the per-model rollout kernel (CustomEnv.plugin_path(plan_models=True))."""
+        the plugin that carries the per-model rollout kernel (CustomEnv.plugin_path(plan_models=True)).
+        ensemble: dict(models=, hyp=, aggregate=, alpha=) -- a model ensemble bound at creation (set_ensemble); a custom environment's
+        context is then created on the plugin that carries the ensemble rollout kernel (plan_ensemble=True)."""
         import torch
         self.kernel_rng = bool(kernel_rng)
         self._rng_counter = 0
@@ -84,7 +86,12 @@ class MBDPI:
         # a rank's rollout scratch is sized by its own shard, not by the global sample count
         extra = {}
         if hasattr(env, "context_kwargs"):   # (custom envs: their task plugin, envs/custom_env.py)
-            extra = env.context_kwargs(plan_models=True) if models is not None else env.context_kwargs()
+            if models is not None and ensemble is not None:
+                raise ValueError("MBDPI: models= (set_models) and ensemble= (set_ensemble) exclude each other")
+            if ensemble is not None:
+                extra = env.context_kwargs(plan_ensemble=True)
+            else:
+                extra = env.context_kwargs(plan_models=True) if models is not None else env.context_kwargs()
         self.ctx = _lib.Context(env.make_model(), env.make_task(), self.cfg, device,
                                 n_local_cap=None if self.world == 1 else self._per, options=options, **extra)
         if hasattr(env, "bind_device"):
@@ -99,6 +106,36 @@ class MBDPI:
         self.model_of = None
         if models is not None:
             self.set_models(models, model_of, model_per)
+        self.hyp = None
+        if ensemble is not None:
+            unknown = sorted(set(ensemble) - {"models", "hyp", "aggregate", "alpha"})
+            if unknown or "models" not in ensemble:
+                raise ValueError(f"MBDPI: ensemble is dict(models=, hyp=, aggregate=, alpha=); got keys {sorted(ensemble)}")
+            self.set_ensemble(**ensemble)
+
+    # ---- robust planning over a model ensemble (dial_set_plan_ensemble; csrc/plan_ens_kernel.h)
+    def set_ensemble(self, models, hyp=None, aggregate: str = "mean", alpha: float = 1.0):
+        """Bind a model ensemble: `models` a list of V compiled model dicts (mjcf.vary_model(env.sys.model, ...)), `hyp` the
+        hypotheses -- [R] indices shared by all plans, or [n_plans][R]; None: all V models in order.  Every candidate of
+        reverse_once / reverse_once_batch is then rolled out under all R hypotheses of its plan and weighted by the aggregate of its R
+        rewards: "mean", "min", or "cvar" (the mean of the ceil(alpha R) worst).  The bars are the weighted means of the trajectories
+        under hypothesis 0, the plan's nominal model.  Every dict gets the env's timestep; env.step and the plant keep their own
+        model.  models None unbinds.  Returns the hypotheses bound."""
+        if models is None:
+            self.ctx.set_plan_ensemble(None)
+            self.hyp = None
+            return None
+        if self.world > 1 or self._force_sharded:
+            raise NotImplementedError("set_ensemble: model ensembles run on one rank (sharded contexts are not supported)")
+        dt = float(self.env.make_model().timestep)
+        structs = []
+        for m in models:
+            st = _abi.make_model(m)
+            st.timestep = dt
+            structs.append(st)
+        index = _lib.plan_ensemble_index(hyp, len(structs), self.n_plans)
+        self.hyp = self.ctx.set_plan_ensemble(structs, index, aggregate, alpha)
+        return self.hyp
 
     # ---- planner model ensembles (dial_set_plan_models; csrc/plan_var_kernel.h)
     def set_models(self, models, model_of=None, per: str = "plan"):
@@ -327,8 +364,55 @@ def plan_models_settings(block: Dict[str, Any], model: Dict[str, Any], n_plans: 
     return models, index, per
 
 
+_PLAN_ENSEMBLE_KEYS = ("variants", "hypotheses", "aggregate", "alpha")
+
+
+def plan_ensemble_settings(block: Dict[str, Any], model: Dict[str, Any], n_plans: int):
+    """A `plan_ensemble` block of the driver's YAML -> dict(models=, hyp=, aggregate=, alpha=) for MBDPI(ensemble=):
+        variants: [ {...}, ... ]      each entry the keywords of mjcf.vary_model; {} is the env's model
+        hypotheses: [...]             optional; R indices shared by all plans, or one list of R per plan; default: all variants in order
+        aggregate: mean | min | cvar  (default mean)
+        alpha: 0.5                    cvar only: the tail's share, in (0, 1] (default 1)
+    Raises ValueError on unknown keys, an empty variant list, whatever vary_model refuses, bad indices, an unknown aggregate and an
+    alpha outside (0, 1]."""
+    from dial_mpc_amd.deploy.dial_sim import sim_model_settings
+    if not isinstance(block, dict):
+        raise ValueError(f"plan_ensemble is a mapping; got {type(block).__name__}")
+    unknown = sorted(set(block) - set(_PLAN_ENSEMBLE_KEYS))
+    if unknown:
+        raise ValueError(f"plan_ensemble: unknown keys {unknown}; known: {list(_PLAN_ENSEMBLE_KEYS)}")
+    aggregate = block.get("aggregate", "mean")
+    if aggregate not in _lib.ENSEMBLE_AGGREGATES:
+        raise ValueError(f"plan_ensemble: aggregate = {aggregate!r}; {sorted(_lib.ENSEMBLE_AGGREGATES)} are allowed")
+    alpha = block.get("alpha", 1.0)
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 < float(alpha) <= 1.0:
+        raise ValueError(f"plan_ensemble: alpha = {alpha!r}; a number in (0, 1] is allowed")
+    variants = block.get("variants")
+    if not isinstance(variants, (list, tuple)) or len(variants) < 1:
+        raise ValueError("plan_ensemble: variants is a non-empty list of mjcf.vary_model keyword mappings ({} is the env's model)")
+    models = []
+    for v, entry in enumerate(variants):
+        try:
+            models.append(sim_model_settings({} if entry is None else entry, model))
+        except ValueError as e:
+            raise ValueError(f"plan_ensemble: variant {v}: {str(e).replace('sim_model: ', '').replace('sim_model ', 'it ')}") from None
+    try:
+        hyp = _lib.plan_ensemble_index(block.get("hypotheses"), len(models), int(n_plans))
+    except ValueError as e:
+        raise ValueError(str(e).replace("plan ensemble: hyp", "plan_ensemble: hypotheses").replace("plan ensemble:", "plan_ensemble:")) from None
+    return dict(models=models, hyp=hyp, aggregate=aggregate, alpha=float(alpha))
+
+
 def _plan_models_kw(config_dict, dial_config, env, n_plans: int) -> Dict[str, Any]:
-    """The MBDPI keywords of the YAML's optional plan_models block; {} when it is absent (nothing is bound)."""
+    """The MBDPI keywords of the YAML's optional plan_models or plan_ensemble block; {} when both are absent (nothing is bound)."""
+    ens = config_dict.get("plan_ensemble")
+    if ens is not None:
+        if config_dict.get("plan_models") is not None:
+            raise ValueError("plan_models and plan_ensemble exclude each other: keep one of the two blocks")
+        kw = plan_ensemble_settings(ens, env.sys.model, n_plans)
+        print(f"planner ensemble: {len(kw['models'])} variants, hypotheses of plan 0 = {kw['hyp'][0].tolist()}, aggregate = {kw['aggregate']}"
+              + (f" (alpha = {kw['alpha']})" if kw["aggregate"] == "cvar" else ""))
+        return dict(ensemble=kw)
     block = config_dict.get("plan_models")
     if block is None:
         return {}

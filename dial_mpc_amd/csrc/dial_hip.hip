@@ -27,6 +27,7 @@
 #include "plant_dist_kernel.h"
 #include "plant_var_kernel.h"
 #include "plan_var_kernel.h"
+#include "plan_ens_kernel.h"
 #include "plugin_ops.h"
 
 // the kernels are compiled in their own translation units, one per robot family (kern_family.hip, built in parallel)
@@ -367,6 +368,14 @@ struct dial_ctx {
   int32_t* plan_model_of = nullptr;        // the index int32[plan_models_rows]; nullptr: every rollout runs the context's own model
   int plan_models_V = 0, plan_models_rows = 0, plan_models_mode = 0;
   dial_plan_var_launch_fn plan_launch = nullptr;   // the kernel's launch function, looked up when the models were bound
+  const dial_plugin_plan_ens* plug_plan_ens = nullptr;       // inst 7: the plugin's ensemble rollout kernel, nullptr: built without one
+  void* ens_models = nullptr;              // model ensemble (dial_set_plan_ensemble), context-owned: V blocks of constants as above,
+  int32_t* ens_hyp = nullptr;              // the hypotheses int32[ens_rows][ens_R] and the raw rewards [ens_R][ens_rows][Nsample + 1]
+  float* ens_raw = nullptr;                // (a launch of M <= ens_rows plans fills [ens_R][M][Nsample + 1] of it); nullptr: nothing bound
+  int ens_V = 0, ens_rows = 0, ens_R = 0, ens_mode = 0, ens_k = 0;   // ens_k: the CVaR tail's size, clamp(ceil(alpha R), 1, R)
+  int ens_last_M = 0;                      // plans of the last ensemble launch since binding (dial_get_ensemble_rewards), 0: none yet
+  dial_plan_ens_launch_fn ens_launch = nullptr;          // looked up when the ensemble was bound
+  dial_plan_ens_aggregate_fn ens_aggregate = nullptr;    // libdialplanens.so's aggregation launcher (plugin contexts too)
   std::vector<float> user_params;          // inst 7: the current user parameters and reference-table binding, as dial_create_plugin /
   const float* user_table = nullptr;       // dial_set_user_params / dial_set_user_table last set them (dial_set_plant_models writes
   int user_table_rows = 0, user_table_cols = 0, user_table_row0 = 0, user_table_mode = 0;   // them into every block it builds)
@@ -485,7 +494,7 @@ void dial_destroy(dial_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   void* ptrs[] = {ctx->dcm, ctx->dtask, ctx->dcfg, ctx->prof, ctx->next, ctx->relay_buf, ctx->relay_flag, ctx->Y0s, ctx->rewss, ctx->rews, ctx->qss,
                   ctx->qdss,   ctx->xss,   ctx->weights, ctx->partial, ctx->ovf, ctx->slice_buf, ctx->slice_flag, ctx->work_stat,
-                  ctx->plant_models, ctx->plant_model_of, ctx->plan_models, ctx->plan_model_of};
+                  ctx->plant_models, ctx->plant_model_of, ctx->plan_models, ctx->plan_model_of, ctx->ens_models, ctx->ens_hyp, ctx->ens_raw};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -572,8 +581,13 @@ int dial_create_plugin(dial_ctx** out, const dial_model* model, const dial_task*
   if (int rc = plugin_table(h, plugin_path, DIAL_PLUGIN_PLAN_VAR_SYMBOL, "plan-models table", DIAL_PLUGIN_PLAN_VAR_VERSION, &pnv)) return rc;
   if (pnv && (pnv->cmodel_bytes != ops->cmodel_bytes || pnv->nq != model->nq || pnv->nv != model->nv || pnv->nu != model->nu || !pnv->launch))
     return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's plan-models table was built against another version of the library (ABI mismatch; rebuild it)");
+  // the ensemble rollout kernel's table: an eighth symbol, exported only by a plugin built with build_plugin(plan_ensemble=True)
+  const dial_plugin_plan_ens* pne;
+  if (int rc = plugin_table(h, plugin_path, DIAL_PLUGIN_PLAN_ENS_SYMBOL, "plan-ensemble table", DIAL_PLUGIN_PLAN_ENS_VERSION, &pne)) return rc;
+  if (pne && (pne->cmodel_bytes != ops->cmodel_bytes || pne->nq != model->nq || pne->nv != model->nv || pne->nu != model->nu || !pne->launch))
+    return fail(nullptr, DIAL_ERR_ARG, "dial_create_plugin: the plugin's plan-ensemble table was built against another version of the library (ABI mismatch; rebuild it)");
   const int rc = create_impl(out, model, task, cfg, device, -1, opts, ops, params, n_params);
-  if (rc == DIAL_OK) { (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; (*out)->plug_plant = pla; (*out)->plug_plant_dist = pld; (*out)->plug_plant_var = plv; (*out)->plug_plan_var = pnv; }
+  if (rc == DIAL_OK) { (*out)->plug_plan_ens = pne; (*out)->plug_ctrl = ctl; (*out)->plug_table = tab; (*out)->plug_plant = pla; (*out)->plug_plant_dist = pld; (*out)->plug_plant_var = plv; (*out)->plug_plan_var = pnv; }
   return rc;
 }
 
@@ -600,6 +614,9 @@ int dial_set_user_params(dial_ctx* ctx, const float* params, int n) {
   if (ctx->plan_models)
     return fail(ctx, DIAL_ERR_ARG, "dial_set_user_params: plan models are bound, and their constants carry a copy of the parameters; unbind first "
                                    "(dial_set_plan_models(ctx, NULL, 0, NULL, 0, 0)), then bind again");
+  if (ctx->ens_models)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_user_params: a plan ensemble is bound, and its constants carry a copy of the parameters; unbind first "
+                                   "(dial_set_plan_ensemble(ctx, NULL, 0, NULL, 0, 0, 0, 0)), then bind again");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->plug->set_params(ctx->plug_cm.data(), params, n);
   ctx->user_params.assign(params, params + n);
@@ -627,6 +644,9 @@ int dial_set_user_table(dial_ctx* ctx, const float* table, int rows, int cols, i
   if (ctx->plan_models)
     return fail(ctx, DIAL_ERR_ARG, "dial_set_user_table: plan models are bound, and their constants carry a copy of the table's binding; unbind first "
                                    "(dial_set_plan_models(ctx, NULL, 0, NULL, 0, 0)), then bind again");
+  if (ctx->ens_models)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_user_table: a plan ensemble is bound, and its constants carry a copy of the table's binding; unbind first "
+                                   "(dial_set_plan_ensemble(ctx, NULL, 0, NULL, 0, 0, 0, 0)), then bind again");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->plug_table->set_table(ctx->plug_cm.data(), table, rows, cols, row0, mode);
   ctx->user_table = table; ctx->user_table_rows = rows; ctx->user_table_cols = cols; ctx->user_table_row0 = row0; ctx->user_table_mode = mode;
@@ -1078,7 +1098,10 @@ int dial_get_rollout_ms(dial_ctx* ctx, double* total_ms, int* launches) {
 }
 
 static bool opt_no_queue(const dial_ctx* ctx) { return ctx->opt.no_queue != 0; }
-static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hipStream_t st) {
+// ens_M > 0 (the robust iterations of a context with a plan ensemble bound, reverse_once_ens): io_in describes the grouped launch of
+// ens_M plans and B = ens_M (Nsample + 1); the launch is the ensemble kernel's R x B wavefronts.  Every other caller passes 0 and
+// never sees the ensemble.
+static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hipStream_t st, int ens_M = 0) {
   // the launch record (dial_debug_last_launch): reset first, so that a call that returns before launching leaves blocks = 0
   int* ll = ctx->last_launch;
   for (int k = 0; k < DIAL_LAUNCH_FIELDS; k++) ll[k] = 0;
@@ -1097,6 +1120,37 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
     e1 = ctx->events[ctx->events_used].second;
     ctx->events_used++;
     HIP_TRY(ctx, hipEventRecord(e0, st));
+  }
+  if (ens_M > 0) {   // (plan_ens_kernel.h; mutually exclusive with dial_set_plan_models)
+    const auto refuse = [&](int code, const std::string& msg) { if (ctx->timing) ctx->events_used--; return fail(ctx, code, msg); };
+    const int R = ctx->ens_R;
+    const long long grid = (long long)R * B;
+    ll[LF_ROLLOUTS] = (int)grid;
+    if (ctx->trace)
+      return refuse(DIAL_ERR_UNSUPPORTED, "rollout launch: a plan ensemble is bound and so is a state trace; the ensemble rollout kernel has no trace "
+                                             "instantiation (unbind one: dial_set_state_trace(ctx, NULL, 0) or dial_set_plan_ensemble(ctx, NULL, 0, NULL, 0, 0, 0, 0))");
+    if (ens_M > ctx->ens_rows)
+      return refuse(DIAL_ERR_ARG, "rollout launch: M = " + std::to_string(ens_M) + " plans, but the bound plan ensemble has hypotheses for " +
+                                     std::to_string(ctx->ens_rows) + " plans (dial_set_plan_ensemble)");
+    dial::RolloutIO io = io_in;
+    io.plan_params = ctx->plan_params;
+    io.con_cap = ctx->ovf ? ctx->con_cap : 0;
+    io.ovf = ctx->ovf;
+    io.ovf_words = ctx->ovf_words;
+    if (io.ovf && grid > ctx->ovf_slots)
+      return refuse(DIAL_ERR_ARG, "rollout launch: the plan ensemble's R x M x (Nsample + 1) = " + std::to_string(grid) + " wavefronts exceed the context's " +
+                                     std::to_string(ctx->ovf_slots) + " overflow areas; a context created with dial_options.plan_cap >= M x R = " +
+                                     std::to_string(ens_M * R) + " provides them");
+    size_t lds = ctx->cm_bytes + (size_t)ctx->ws_words * sizeof(float);   // the staged constants + ONE workspace
+#ifdef DIAL_PROFILE
+    lds += 16 + 32 * sizeof(unsigned long long);
+#endif
+    ll[LF_WPB] = 1; ll[LF_BLOCKS] = (int)grid; ll[LF_CON_CAP] = io.con_cap;
+    HIP_TRY(ctx, ctx->ens_launch(lds, st, ctx->ens_models, (const dial_task*)ctx->dtask, (const dial_cfg*)ctx->dcfg, &io, ens_M, R, ctx->ws_words,
+                                 ctx->ens_hyp, ctx->ens_raw));
+    ctx->ens_last_M = ens_M;
+    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(e1, st));
+    return DIAL_OK;
   }
   // planner models are bound (dial_set_plan_models): the kernel of plan_var_kernel.h -- one wavefront per rollout on a plain grid,
   // every rollout on its own block of constants -- instead of every path below (none of them can change constants inside a launch)
@@ -1503,11 +1557,39 @@ int dial_shard_pack_rewards(dial_ctx* ctx, const float* gathered, int world, int
   return DIAL_OK;
 }
 
+// One robust iteration of M plans on a context with a plan ensemble bound (dial_set_plan_ensemble; the callers have checked the
+// arguments): the ensemble rollout launch -> raw [R][M][N + 1]; the aggregation -> rews [M][N + 1]; then the tail of every other
+// call, unchanged, on the aggregated rewards and the rows of hypothesis 0 (dense grouped layout).
+static int reverse_once_ens(dial_ctx* ctx, const float* states, const float* Ybar_in, const float* noise_scale, int ns, const float* eps,
+                            int use_rng, uint64_t seed, uint32_t counter, int M, float* Ybar_out, float* rews, float* qbar, float* qdbar,
+                            float* xbar, void* stream) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int N = ctx->hc.Nsample;
+  const bool bars = qbar || qdbar || xbar;
+  dial::RolloutIO io{states, nullptr, eps, Ybar_in, noise_scale, ns, N, ctx->T, ctx->Hn1,
+                     ctx->Y0s, ctx->rewss, nullptr, bars ? ctx->qss : nullptr, bars ? ctx->qdss : nullptr,
+                     bars ? ctx->xss : nullptr, ctx->prof, use_rng, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), counter, 0};
+  io.plan_rollouts = N + 1;
+  hipStream_t st = (hipStream_t)stream;
+  if (!bars) ctx->rows_stale = "the last rollout launch formed the mean action only (a robust iteration without bars): it wrote no per-step states";
+  if (int rc = launch_rollout(ctx, io, M * (N + 1), st, M)) return rc;
+  if (bars) ctx->rows_stale = nullptr;
+  HIP_TRY(ctx, ctx->ens_aggregate(st, ctx->ens_raw, rews, ctx->ens_R, M * (N + 1), ctx->ens_mode, ctx->ens_k));
+  hipLaunchKernelGGL(weights_kernel, dim3(M), dim3(WK_THREADS), 0, st, (const float*)rews, N + 1, ctx->hc.temp_sample, ctx->weights, (const float*)nullptr, 0, (float*)nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  return launch_wsum(ctx, ctx->weights, N + 1, 0, N, N, Ybar_out, qbar, qdbar, xbar, st, !bars, M);
+}
+
 static int reverse_once_impl(dial_ctx* ctx, const float* state, const float* Ybar_in, const float* noise_scale, int ns,
                              const float* eps, int use_rng, uint64_t seed, uint32_t counter, float* Ybar_out,
                              float* rews, float* qbar, float* qdbar, float* xbar, void* stream, const char* who) {
   if (!ctx || !Ybar_out || !rews) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": null argument");
   if (!ctx->has_cfg) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": context was created without a dial_cfg");
+  if (ctx->ens_models) {   // a plan ensemble is bound: one robust iteration with row 0's hypotheses
+    if (!state || !Ybar_in || !noise_scale || (!eps && !use_rng)) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": null argument");
+    if (ns != 1 && ns != ctx->Hn1) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": noise_scale must have 1 or Hnode+1 entries");
+    return reverse_once_ens(ctx, state, Ybar_in, noise_scale, ns, eps, use_rng, seed, counter, 1, Ybar_out, rews, qbar, qdbar, xbar, stream);
+  }
   const int N = ctx->hc.Nsample;
   // qbar == qdbar == xbar == NULL: the caller wants the mean action only (every annealing iteration of a plan but the last,
   // dial_core.py:262-264 / dial_plan.py:214-215 read the bars of the LAST one) -- the rollouts then do not write their
@@ -1550,6 +1632,8 @@ static int reverse_once_batch_impl(dial_ctx* ctx, const float* states, const flo
   if (ns != 1 && ns != ctx->Hn1) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": ns = " + std::to_string(ns) + " must be 1 or Hnode+1 = " + std::to_string(ctx->Hn1));
   if (!states || !Ybar_in || !noise_scale || (!eps && !use_rng) || !Ybar_out || !rews) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": null argument");
   if (int rc = check_plan_rows(ctx, M, who)) return rc;
+  if (ctx->ens_models)   // a plan ensemble is bound: one robust iteration of the M plans
+    return reverse_once_ens(ctx, states, Ybar_in, noise_scale, ns, eps, use_rng, seed, counter, M, Ybar_out, rews, qbar, qdbar, xbar, stream);
   if (M == 1)
     return reverse_once_impl(ctx, states, Ybar_in, noise_scale, ns, eps, use_rng, seed, counter, Ybar_out, rews, qbar, qdbar, xbar, stream, who);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2032,6 +2116,9 @@ int dial_set_plan_models(dial_ctx* ctx, const dial_model* models, int V, const i
     ctx->plan_launch = nullptr;
     return DIAL_OK;
   }
+  if (ctx->ens_models)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: a plan ensemble is bound (dial_set_plan_ensemble); unbind it first "
+                                   "(dial_set_plan_ensemble(ctx, NULL, 0, NULL, 0, 0, 0, 0))");
   if (V < 1 || V > DIAL_MAX_PLAN_MODELS)
     return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: V = " + std::to_string(V) + " is outside 1 .. DIAL_MAX_PLAN_MODELS");
   if (rows < 1) return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_models: rows = " + std::to_string(rows) + " must be >= 1");
@@ -2083,6 +2170,180 @@ int dial_set_plan_models(dial_ctx* ctx, const dial_model* models, int V, const i
   ctx->plan_models_mode = mode;
   ctx->plan_launch = launch;
 #endif
+  return DIAL_OK;
+}
+
+#ifndef DIAL_IEEE_BUILD
+// libdialplanens.so (plan_ens_family.hip, plan_ens_aggregate.hip): the ensemble rollout kernels and the aggregation kernel, looked up
+// the first time an ensemble is bound
+struct PlanEnsLib {
+  const dial_plan_ens_ops* ops = nullptr;
+  std::string err;
+};
+static PlanEnsLib plan_ens_load() {
+  PlanEnsLib r;
+  Dl_info info{};
+  std::string dir = ".";
+  if (dladdr((const void*)&plan_ens_load, &info) && info.dli_fname) {
+    dir = info.dli_fname;
+    const size_t slash = dir.rfind('/');
+    dir = slash == std::string::npos ? "." : dir.substr(0, slash);
+  }
+  const std::string path = dir + "/libdialplanens.so";
+  void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);   // (never dlclose'd: the runtime holds its code objects)
+  if (!h) { r.err = "cannot load " + path + " (build it: dial_mpc_amd._lib.build()): " + dlerror(); return r; }
+  dial_plan_ens_entry entry = (dial_plan_ens_entry)dlsym(h, DIAL_PLAN_ENS_SYMBOL);
+  const dial_plan_ens_ops* o = entry ? entry() : nullptr;
+  if (!o) r.err = path + " does not export " DIAL_PLAN_ENS_SYMBOL;
+  else if (o->abi_version != DIAL_PLAN_ENS_ABI_VERSION || o->sizeof_model != sizeof(dial_model) || o->sizeof_task != sizeof(dial_task) ||
+           o->sizeof_cfg != sizeof(dial_cfg) || o->sizeof_io != sizeof(dial::RolloutIO) || !o->aggregate)
+    r.err = path + " was built against another version of the library (rebuild it)";
+  else r.ops = o;
+  return r;
+}
+static const PlanEnsLib& plan_ens_lib() {
+  static const PlanEnsLib lib = plan_ens_load();   // (once per process, thread-safe initialisation)
+  return lib;
+}
+#endif
+
+// The ensemble rollout kernel's launch function of a context -- the plugin's eighth table, or libdialplanens.so's entry of the
+// context's instantiation -- and the aggregation launcher, which is libdialplanens.so's for every context.  false with the reason
+// in `why` (DIAL_ERR_UNSUPPORTED).
+static bool plan_ens_fns_of(dial_ctx* ctx, dial_plan_ens_launch_fn& launch, dial_plan_ens_aggregate_fn& aggregate, std::string& why) {
+#ifdef DIAL_IEEE_BUILD
+  (void)ctx; (void)launch; (void)aggregate;
+  why = "the IEEE measurement build carries no ensemble rollout kernel (use the product library)";
+  return false;
+#else
+  if (ctx->plug && !ctx->plug_plan_ens) {
+    why = "the context's task plugin does not export " DIAL_PLUGIN_PLAN_ENS_SYMBOL " (build it with build_plugin(plan_ensemble=True); "
+          "CustomEnv.plugin_path(plan_ensemble=True) does)";
+    return false;
+  }
+  const PlanEnsLib& lib = plan_ens_lib();
+  if (!lib.ops) { why = lib.err; return false; }
+  aggregate = lib.ops->aggregate;
+  if (ctx->plug) { launch = ctx->plug_plan_ens->launch; return true; }
+  if (ctx->inst < 0 || ctx->inst >= DIAL_PLAN_ENS_INSTS || lib.ops->cmodel_bytes[ctx->inst] != ctx->dcm_bytes) {
+    why = "libdialplanens.so does not match this library's constants (rebuild both)";
+    return false;
+  }
+  if (!lib.ops->launch[ctx->inst]) {
+    why = "libdialplanens.so carries no ensemble rollout kernel for kernel instantiation " + std::to_string(ctx->inst);
+    return false;
+  }
+  launch = lib.ops->launch[ctx->inst];
+  return true;
+#endif
+}
+
+int dial_set_plan_ensemble(dial_ctx* ctx, const dial_model* models, int V, const int32_t* hyp, int rows, int R, int aggregate, float alpha) {
+  if (!ctx) return fail(nullptr, DIAL_ERR_ARG, "dial_set_plan_ensemble: null context");
+  if (!models && !hyp && V == 0 && rows == 0 && R == 0 && aggregate == 0 && alpha == 0.f) {   // unbind
+    if (ctx->ens_models) {
+      HIP_TRY(ctx, hipSetDevice(ctx->device));
+      HIP_TRY(ctx, hipDeviceSynchronize());   // (launches in flight read the blocks)
+      (void)hipFree(ctx->ens_models);
+      (void)hipFree(ctx->ens_hyp);
+      (void)hipFree(ctx->ens_raw);
+    }
+    ctx->ens_models = nullptr;
+    ctx->ens_hyp = nullptr;
+    ctx->ens_raw = nullptr;
+    ctx->ens_V = ctx->ens_rows = ctx->ens_R = ctx->ens_mode = ctx->ens_k = ctx->ens_last_M = 0;
+    ctx->ens_launch = nullptr;
+    ctx->ens_aggregate = nullptr;
+    return DIAL_OK;
+  }
+  if (ctx->plan_models)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_ensemble: plan models are bound (dial_set_plan_models); unbind them first "
+                                   "(dial_set_plan_models(ctx, NULL, 0, NULL, 0, 0))");
+  if (V < 1 || V > DIAL_MAX_PLAN_MODELS)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_ensemble: V = " + std::to_string(V) + " is outside 1 .. DIAL_MAX_PLAN_MODELS");
+  if (R < 1 || R > DIAL_MAX_ENSEMBLE)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_ensemble: R = " + std::to_string(R) + " is outside 1 .. DIAL_MAX_ENSEMBLE = " + std::to_string(DIAL_MAX_ENSEMBLE));
+  if (!ctx->has_cfg) return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_ensemble: context was created without a dial_cfg (it launches no rollouts)");
+  if (ctx->B_cap < ctx->hc.Nsample + 1)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_ensemble: the context is sharded (n_local_cap < Nsample)");
+  if (rows < 1 || rows > ctx->plan_cap)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_ensemble: rows = " + std::to_string(rows) + " is outside 1 .. the context's plan capacity " +
+                                   std::to_string(ctx->plan_cap) + " (dial_options.plan_cap; one row of hypotheses per plan)");
+  if (!models || !hyp)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_ensemble: a null pointer with V = " + std::to_string(V) + ", rows = " + std::to_string(rows) +
+                                   ", R = " + std::to_string(R) + " (NULL, 0, NULL, 0, 0, 0, 0 unbinds)");
+  if (aggregate != DIAL_ENSEMBLE_MEAN && aggregate != DIAL_ENSEMBLE_MIN && aggregate != DIAL_ENSEMBLE_CVAR)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_ensemble: unknown aggregate " + std::to_string(aggregate) +
+                                   " (DIAL_ENSEMBLE_MEAN, DIAL_ENSEMBLE_MIN or DIAL_ENSEMBLE_CVAR)");
+  if (aggregate == DIAL_ENSEMBLE_CVAR && !(alpha > 0.f && alpha <= 1.f))
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_ensemble: alpha = " + std::to_string(alpha) + " is outside (0, 1] (DIAL_ENSEMBLE_CVAR)");
+  for (int g = 0; g < rows; g++)
+    for (int r = 0; r < R; r++) {
+      const int32_t v = hyp[(size_t)g * R + r];
+      if (v < 0 || v >= V)
+        return fail(ctx, DIAL_ERR_ARG, "dial_set_plan_ensemble: hyp[" + std::to_string(g) + "][" + std::to_string(r) + "] = " + std::to_string(v) +
+                                       " is outside 0 .. V - 1 = " + std::to_string(V - 1));
+    }
+  std::string why;
+  dial_plan_ens_launch_fn launch = nullptr;
+  dial_plan_ens_aggregate_fn agg = nullptr;
+  if (!plan_ens_fns_of(ctx, launch, agg, why)) return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_set_plan_ensemble: " + why);
+#ifndef DIAL_IEEE_BUILD
+  std::vector<char> blocks;
+  if (int rc = model_blocks(ctx, models, V, "dial_set_plan_ensemble", blocks)) return rc;
+  // the CVaR tail: the k = clamp(ceil(alpha R), 1, R) worst rewards of a candidate
+  int k = R;
+  if (aggregate == DIAL_ENSEMBLE_CVAR) {
+    k = (int)ceil((double)alpha * (double)R);
+    k = k < 1 ? 1 : (k > R ? R : k);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  void* dblocks = nullptr;
+  int32_t* dhyp = nullptr;
+  float* draw = nullptr;
+  const size_t hyp_bytes = (size_t)rows * R * sizeof(int32_t), raw_bytes = (size_t)R * rows * (ctx->hc.Nsample + 1) * sizeof(float);
+  hipError_t e = hipMalloc(&dblocks, blocks.size());
+  if (e == hipSuccess) e = hipMalloc((void**)&dhyp, hyp_bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&draw, raw_bytes);
+  if (e == hipSuccess) e = hipMemcpy(dblocks, blocks.data(), blocks.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dhyp, hyp, hyp_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // (launches in flight read the previous binding's buffers)
+  if (e != hipSuccess) {
+    if (dblocks) (void)hipFree(dblocks);
+    if (dhyp) (void)hipFree(dhyp);
+    if (draw) (void)hipFree(draw);
+    return fail(ctx, DIAL_ERR_HIP, std::string("dial_set_plan_ensemble: uploading the constants failed: ") + hipGetErrorString(e));
+  }
+  if (ctx->ens_models) (void)hipFree(ctx->ens_models);
+  if (ctx->ens_hyp) (void)hipFree(ctx->ens_hyp);
+  if (ctx->ens_raw) (void)hipFree(ctx->ens_raw);
+  ctx->ens_models = dblocks;
+  ctx->ens_hyp = dhyp;
+  ctx->ens_raw = draw;
+  ctx->ens_V = V;
+  ctx->ens_rows = rows;
+  ctx->ens_R = R;
+  ctx->ens_mode = aggregate;
+  ctx->ens_k = k;
+  ctx->ens_last_M = 0;
+  ctx->ens_launch = launch;
+  ctx->ens_aggregate = agg;
+#endif
+  return DIAL_OK;
+}
+
+int dial_get_ensemble_rewards(dial_ctx* ctx, float* out, int M, void* stream) {
+  if (!ctx) return fail(nullptr, DIAL_ERR_ARG, "dial_get_ensemble_rewards: null context");
+  if (!out) return fail(ctx, DIAL_ERR_ARG, "dial_get_ensemble_rewards: null argument");
+  if (!ctx->ens_models) return fail(ctx, DIAL_ERR_ARG, "dial_get_ensemble_rewards: no plan ensemble is bound (dial_set_plan_ensemble)");
+  if (ctx->ens_last_M == 0)
+    return fail(ctx, DIAL_ERR_ARG, "dial_get_ensemble_rewards: no robust iteration has run since the ensemble was bound");
+  if (M != ctx->ens_last_M)
+    return fail(ctx, DIAL_ERR_ARG, "dial_get_ensemble_rewards: M = " + std::to_string(M) + ", the last ensemble launch had " +
+                                   std::to_string(ctx->ens_last_M) + " plans");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->ens_raw, (size_t)ctx->ens_R * M * (ctx->hc.Nsample + 1) * sizeof(float), hipMemcpyDeviceToDevice,
+                              (hipStream_t)stream));
   return DIAL_OK;
 }
 

@@ -15,6 +15,9 @@
 // (plant_var_kernel.h: per-plant model constants, dial_set_plant_models) and a sixth table, dial_plugin_plant_var.
 // -DDIAL_PLUGIN_PLAN_VAR=1 (build_plugin(plan_models=True), with or without a plant) adds rollout_var_kernel<DimsPlugin>
 // (plan_var_kernel.h: per-plan / per-sample planner models, dial_set_plan_models) and a seventh table, dial_plugin_plan_var.
+// -DDIAL_PLUGIN_PLAN_ENS=1 (build_plugin(plan_ensemble=True), after every other define) adds rollout_ens_kernel<DimsPlugin>
+// (plan_ens_kernel.h: robust planning over a model ensemble, dial_set_plan_ensemble) and an eighth table, dial_plugin_plan_ens; the
+// aggregation kernel of such a context is libdialplanens.so's.
 #include "plugin_ops.h"
 #ifndef DIAL_PLUGIN_PLANT
 #define DIAL_PLUGIN_PLANT 0
@@ -45,6 +48,12 @@
 #endif
 #if DIAL_PLUGIN_PLAN_VAR
 #include "plan_var_kernel.h"
+#endif
+#ifndef DIAL_PLUGIN_PLAN_ENS
+#define DIAL_PLUGIN_PLAN_ENS 0
+#endif
+#if DIAL_PLUGIN_PLAN_ENS
+#include "plan_ens_kernel.h"
 #endif
 #include "dial_plugin_dims.h"
 #include "dial_user_reward.hip"
@@ -123,5 +132,14 @@ template __global__ void rollout_var_kernel<DimsPlugin>(const CModel<DimsPlugin>
 
 extern "C" __attribute__((visibility("default"))) const dial_plugin_plan_var* dial_plugin_plan_var_v1(void) {
   return PluginPlanVar<DimsPlugin>::table();
+}
+#endif
+
+#if DIAL_PLUGIN_PLAN_ENS
+template __global__ void rollout_ens_kernel<DimsPlugin>(const CModel<DimsPlugin>*, const dial_task*, const dial_cfg*, dial::RolloutIO, int, int, int,
+                                                         const int32_t*, float*);
+
+extern "C" __attribute__((visibility("default"))) const dial_plugin_plan_ens* dial_plugin_plan_ens_v1(void) {
+  return PluginPlanEns<DimsPlugin>::table();
 }
 #endif

@@ -113,10 +113,21 @@ class CustomEnv(BaseEnv):
     def task_dict(self) -> Dict[str, Any]:
         return dict(super().task_dict(), nfeet=0)
 
-    def plugin_path(self, plan_models: bool = False) -> str:
+    def plugin_path(self, plan_models: bool = False, plan_ensemble: bool = False) -> str:
         """Build (or find in the cache) this env's task plugin.  plan_models=True: the plugin that also carries the rollout kernel with
         per-plan / per-sample model constants (build_plugin(plan_models=True); Context.set_plan_models needs it) -- another library,
-        the default one stays as it is."""
+        the default one stays as it is.  plan_ensemble=True: the plugin that carries the ensemble rollout kernel
+        (build_plugin(plan_ensemble=True); Context.set_plan_ensemble needs it), again a library of its own; with both, both kernels."""
+        if plan_ensemble:
+            cache = getattr(self, "_plan_ens_plugins", None)
+            if cache is None:
+                cache = self._plan_ens_plugins = {}
+            if bool(plan_models) not in cache:
+                from dial_mpc_amd.plugin import build_plugin
+                extra = dict(plan_models=True) if plan_models else {}
+                cache[bool(plan_models)] = build_plugin(self.sys.model, self.reward_source(), control_src=self.control_source(),
+                                                        plan_ensemble=True, **extra)
+            return cache[bool(plan_models)]
         if plan_models:
             if getattr(self, "_plan_var_plugin", None) is None:
                 from dial_mpc_amd.plugin import build_plugin
@@ -201,16 +212,24 @@ class CustomEnv(BaseEnv):
         t = self._table_override if getattr(self, "_table_override", None) is not None else self.make_table()
         return None if t is None else _lib.user_table_array(t)
 
-    def context_kwargs(self, plant: bool = False, disturbance: bool = False, models: bool = False, plan_models: bool = False) -> Dict[str, Any]:
+    def context_kwargs(self, plant: bool = False, disturbance: bool = False, models: bool = False, plan_models: bool = False,
+                       plan_ensemble: bool = False) -> Dict[str, Any]:
         """What a _lib.Context of this env needs beyond (model, task, cfg): its plugin (plant=True: the plant-enabled one, with
         disturbance=True the one that also carries the disturbed plant kernel, with models=True the per-plant-model kernel;
-        plan_models=True: the planner's plugin with the per-model rollout kernel, Context.set_plan_models needs it), parameters and
-        reference table."""
+        plan_models=True: the planner's plugin with the per-model rollout kernel, Context.set_plan_models needs it;
+        plan_ensemble=True: the planner's plugin with the ensemble rollout kernel, Context.set_plan_ensemble needs it), parameters
+        and reference table."""
         from dial_mpc_amd import _lib
         plant = plant or disturbance or models
         if plant and plan_models:
             raise ValueError("context_kwargs: plan_models=True is for the planner's context, plant / disturbance / models for the plant's")
-        kw = dict(plugin=self.plant_plugin_path(disturbance, models) if plant else self.plugin_path(plan_models), user_params=self.user_param_vector())
+        if plant and plan_ensemble:
+            raise ValueError("context_kwargs: plan_ensemble=True is for the planner's context, plant / disturbance / models for the plant's")
+        if plant:
+            path = self.plant_plugin_path(disturbance, models)
+        else:
+            path = self.plugin_path(plan_models, plan_ensemble=True) if plan_ensemble else self.plugin_path(plan_models)
+        kw = dict(plugin=path, user_params=self.user_param_vector())
         table = self._table()
         if table is not None:
             kw.update(user_table=table, table_row0=int(self.table_row0), table_mode=_lib.table_mode(self.table_mode))

@@ -15,7 +15,9 @@ the built-in families' kernel, behind the table of ``csrc/plant_plugin.h``;
 ``plant_models=True`` (implies ``plant=True``) adds the plant kernel with per-plant model constants (``plant_var_kernel`` of
 ``csrc/plant_var_kernel.h``; ``dial_set_plant_models``) and a sixth symbol (``PLANT_VAR_SYMBOL``).
 ``plan_models=True`` adds the rollout kernel with per-plan / per-sample model constants (``rollout_var_kernel`` of
-``csrc/plan_var_kernel.h``; ``dial_set_plan_models``) and a seventh symbol (``PLAN_VAR_SYMBOL``).  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
+``csrc/plan_var_kernel.h``; ``dial_set_plan_models``) and a seventh symbol (``PLAN_VAR_SYMBOL``).
+``plan_ensemble=True`` adds the ensemble rollout kernel (``rollout_ens_kernel`` of ``csrc/plan_ens_kernel.h``;
+``dial_set_plan_ensemble``) and an eighth symbol (``PLAN_ENS_SYMBOL``).  Results are cached under ``build/plugins/<key>/`` (``DIAL_PLUGIN_CACHE`` overrides the root); the key
 hashes every csrc source, ``include/dial_mpc.h``, the reward, the control law (when there is one), the dimensions, the flags and ``hipcc --version``.  hipcc
 cross-compiles, so building needs no GPU.
 """
@@ -42,6 +44,7 @@ PLANT_SYMBOL = "dial_plugin_plant_v1"  # exported only by a plugin built with pl
 PLANT_DIST_SYMBOL = "dial_plugin_plant_dist_v1"  # only with plant_disturbance=True: the disturbed plant kernel's table (dial_set_plant_disturbance)
 PLANT_VAR_SYMBOL = "dial_plugin_plant_var_v1"  # only with plant_models=True: the per-plant-model plant kernel's table (dial_set_plant_models)
 PLAN_VAR_SYMBOL = "dial_plugin_plan_var_v1"  # only with plan_models=True: the per-model rollout kernel's table (dial_set_plan_models)
+PLAN_ENS_SYMBOL = "dial_plugin_plan_ens_v1"  # only with plan_ensemble=True: the ensemble rollout kernel's table (dial_set_plan_ensemble)
 DIM_NAMES = ("nq", "nv", "nu", "nbody", "njnt", "ngeom", "nsite", "ncon", "nlim", "nfri")
 _DIM_MACROS = ("NQ", "NV", "NU", "NB", "NJ", "NG", "NS", "NC", "NL", "NFRI")
 
@@ -126,7 +129,7 @@ def plugin_key(model, reward_src: str, flags: Sequence[str], control_src: Option
 
 def build_plugin(model, reward_src: str, flags: Optional[Sequence[str]] = None, verbose: bool = False,
                  control_src: Optional[str] = None, plant: bool = False, plant_disturbance: bool = False,
-                 plant_models: bool = False, plan_models: bool = False) -> str:
+                 plant_models: bool = False, plan_models: bool = False, plan_ensemble: bool = False) -> str:
     """Compile (or find in the cache) the task plugin of `model` with the reward `reward_src` (HIP source text, or the path of a
     .hip file) and, optionally, the control law `control_src` (the same two forms) -> path of the shared library.  plant=True:
     the plugin also carries the plant simulator's kernel (-DDIAL_PLUGIN_PLANT=1; the define is one of the flags the cache key
@@ -137,7 +140,9 @@ def build_plugin(model, reward_src: str, flags: Optional[Sequence[str]] = None, 
     more; it combines with plant_disturbance=True, and the plugins built without it keep their flags and keys).  plan_models=True adds the
     rollout kernel with per-plan / per-sample model constants (-DDIAL_PLUGIN_PLAN_VAR=1, after every other define:
     csrc/plan_var_kernel.h, dial_set_plan_models; one kernel and one symbol more).  It implies nothing and combines with plant=,
-    plant_disturbance= and plant_models=; the plugins built without it keep their flags and keys.  A compile error in either source raises DialHipError with
+    plant_disturbance= and plant_models=; the plugins built without it keep their flags and keys.  plan_ensemble=True adds the ensemble
+    rollout kernel (-DDIAL_PLUGIN_PLAN_ENS=1, after every other define: csrc/plan_ens_kernel.h, dial_set_plan_ensemble; one kernel and
+    one symbol more) in the same way: it implies nothing, combines with the others and leaves their flags and keys alone.  A compile error in either source raises DialHipError with
     hipcc's own message."""
     import fcntl
     check_model(model)
@@ -150,6 +155,8 @@ def build_plugin(model, reward_src: str, flags: Optional[Sequence[str]] = None, 
         flags.append("-DDIAL_PLUGIN_PLANT_VAR=1")
     if plan_models:
         flags.append("-DDIAL_PLUGIN_PLAN_VAR=1")
+    if plan_ensemble:
+        flags.append("-DDIAL_PLUGIN_PLAN_ENS=1")
     reward = _read_reward(reward_src)
     control = None if control_src is None else _read_reward(control_src)
     key = plugin_key(model, reward, flags, control)[:24]

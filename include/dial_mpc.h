@@ -77,6 +77,10 @@ extern "C" {
 #define DIAL_MAX_PLAN_MODELS 1024 /* dial_set_plan_models: distinct planner models of one binding */
 #define DIAL_PLAN_MODELS_PER_PLAN 0 /* model_of[rows <= plan_cap]: plan g runs models[model_of[g]]; one-plan launches read row 0 */
 #define DIAL_PLAN_MODELS_PER_SAMPLE 1 /* model_of[rows == Nsample + 1]: local rollout nl of EVERY plan runs models[model_of[nl]]; row Nsample is the mean trajectory's */
+#define DIAL_MAX_ENSEMBLE 32      /* hypotheses per plan */
+#define DIAL_ENSEMBLE_MEAN 0
+#define DIAL_ENSEMBLE_MIN  1
+#define DIAL_ENSEMBLE_CVAR 2
 
 /* joint types (MuJoCo numbering) */
 #define DIAL_JNT_FREE 0
@@ -703,6 +707,52 @@ int dial_set_plant_models(dial_ctx* ctx, const dial_model* models, int V, const 
  * the kernel has no trace instantiation).  Go2 batches above 2304 rollouts run this one-rollout-per-wavefront kernel too, not the
  * pair kernel. */
 int dial_set_plan_models(dial_ctx* ctx, const dial_model* models, int V, const int32_t* model_of, int rows, int mode);
+/* Robust planning over a model ensemble: every candidate action sequence of a plan is rolled out under EVERY model hypothesis of
+ * that plan, the per-hypothesis rewards are aggregated per candidate, and the planner's softmax runs on the aggregate.
+ * models:[V] (1 <= V <= DIAL_MAX_PLAN_MODELS) and hyp:[rows][R] (1 <= rows <= the context's plan capacity, 1 <= R <=
+ * DIAL_MAX_ENSEMBLE, 0 <= hyp[g][r] < V) are HOST arrays; the library COPIES them as dial_set_plan_models does (the same blocks of
+ * constants, the same acceptance rule for a model: dial_set_plant_models's, with the context's own timestep).  Plan g's hypotheses
+ * are models[hyp[g][0 .. R-1]]; hypothesis 0 is the plan's NOMINAL model.  aggregate: DIAL_ENSEMBLE_MEAN (expectation),
+ * DIAL_ENSEMBLE_MIN (worst case) or DIAL_ENSEMBLE_CVAR (the mean of the k = clamp(ceil(alpha R), 1, R) worst rewards; alpha in (0, 1],
+ * ignored by the other two).
+ * While bound, dial_reverse_once[_rng] plans with row 0 and dial_reverse_once_batch[_rng] takes M <= rows plans; each call runs one
+ * robust iteration:
+ *   1. ONE rollout launch of R x M x (Nsample + 1) wavefronts, hypothesis-major (csrc/plan_ens_kernel.h, in libdialplanens.so next to
+ *      this library; on a task-plugin context the plugin's own, build_plugin(plan_ensemble=True), behind the optional table
+ *      dial_plugin_plan_ens_v1).  Rollout (r, g, nl) starts from plan g's state, Ybar and noise scale, builds the nodes of plan g's
+ *      sample nl -- the same eps row, or Philox key g Nsample + nl, for every r; nl = Nsample is the mean trajectory -- and runs on
+ *      models[hyp[g][r]].  Its mean reward goes to a raw buffer [R][M][Nsample + 1] the binding owns.  Only the rollouts of r = 0
+ *      also write the candidate nodes, step rewards and per-step states to the context's scratch, in the dense grouped layout; the
+ *      scratch therefore needs M <= plan_cap plans, not M R.  Each rollout equals, bit for bit, the same rollout of a context
+ *      created from its model.
+ *   2. The aggregation: raw -> the caller's rews[M][Nsample + 1], one thread per candidate over its R rewards x_0 .. x_{R-1}:
+ *      MEAN the fp64 sum in index order divided by (double)R, rounded once to fp32; MIN the smallest x_r; CVAR the k smallest in
+ *      ascending order, ties broken by the lower r, summed in fp64 in that order, divided by (double)k, rounded once to fp32.
+ *      A NaN among a candidate's rewards leaves its MIN / CVAR aggregate UNSPECIFIED (the device code does not honour NaNs; the
+ *      plan's softmax is NaN in that case anyway).
+ *   3. The softmax and the weighted means of every other call, unchanged, on the aggregated rews and the rows of r = 0: Ybar_out is
+ *      the robustly weighted mean action; qbar / qdbar / xbar are the robustly weighted means of the trajectories UNDER HYPOTHESIS 0,
+ *      the nominal model of each plan -- the ensemble has one trajectory per hypothesis and no single one to report.
+ * dial_rollout, dial_env_step*, dial_env_reset* and dial_plant_step IGNORE the binding.  Per-plan task parameters
+ * (dial_set_plan_params) still apply; dial_set_timing times the rollout launch; dial_debug_last_launch reports one wavefront per
+ * workgroup and R x M x (Nsample + 1) workgroups.  While bound, dial_set_user_params and dial_set_user_table fail with
+ * DIAL_ERR_ARG (the blocks carry a copy of both: unbind first).
+ * (NULL, 0, NULL, 0, 0, 0, 0) unbinds.  A failed call leaves the previous binding in place.  Synchronises the device.
+ * Fails with DIAL_ERR_ARG and a message that starts with "dial_set_plan_ensemble: " on a null context, V outside
+ * 1 .. DIAL_MAX_PLAN_MODELS, R outside 1 .. DIAL_MAX_ENSEMBLE, rows outside 1 .. plan_cap, a null pointer with non-zero counts, an
+ * index outside 0 .. V - 1 (the message names its position), a rejected model (its index and the reason), an unknown aggregate,
+ * DIAL_ENSEMBLE_CVAR with alpha outside (0, 1], a sharded context (n_local_cap < Nsample) or one created without a dial_cfg, and
+ * while dial_set_plan_models is bound (unbind it first; dial_set_plan_models likewise refuses while an ensemble is bound); with
+ * DIAL_ERR_UNSUPPORTED when libdialplanens.so is missing or stale or has no kernel for the context's family, on a task plugin
+ * without the table, and in the IEEE measurement build.  A launch fails with DIAL_ERR_ARG when M > rows and, on the
+ * capacity-dimension kernel, when its R x M x (Nsample + 1) wavefronts exceed the context's overflow areas (a context created with
+ * plan_cap >= M R provides them), and with DIAL_ERR_UNSUPPORTED while a state trace is bound. */
+int dial_set_plan_ensemble(dial_ctx* ctx, const dial_model* models, int V, const int32_t* hyp /* [rows][R] */,
+                           int rows, int R, int aggregate, float alpha);
+/* The raw per-hypothesis rewards of the context's last ensemble launch: an asynchronous device-to-device copy on `stream` into
+ * out:[R][M][Nsample + 1] (device).  Fails with DIAL_ERR_ARG when no ensemble is bound, when no launch has run since it was bound,
+ * or when M differs from that launch's M. */
+int dial_get_ensemble_rewards(dial_ctx* ctx, float* out /* device, [R][M][Nsample+1] */, int M, void* stream);
 
 /* ABI self-description used by tests: sizeof of the three structs. */
 int dial_abi_sizes(int* model_bytes, int* task_bytes, int* cfg_bytes);
