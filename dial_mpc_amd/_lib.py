@@ -77,7 +77,10 @@ def build(force: bool = False, verbose: bool = False, ieee: bool = False) -> str
         build_plant_var(force=force, verbose=verbose)
         build_plan_var(force=force, verbose=verbose)
         build_plan_ens(force=force, verbose=verbose)
+        build_reward_defer(force=force, verbose=verbose)
+    # (the IEEE measurement variant links the deferred-reward kernel's unit itself: libdialhip_ieee.so's code objects are pinned by nothing)
     return _build_lib(IEEE_LIB_PATH if ieee else LIB_PATH, [(os.path.join(_CSRC, "dial_hip.hip"), [], "dial_hip.o")] +
+                      ([(os.path.join(_CSRC, "reward_defer.hip"), [], "reward_defer.o")] if ieee else []) +
                       [(os.path.join(_CSRC, "kern_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []), f"kern_family_{k}.o")
                        for k in range(N_FAMILIES)], force, verbose, ieee)
 
@@ -128,6 +131,17 @@ def build_plan_var(force: bool = False, verbose: bool = False) -> str:
     models are bound."""
     return _build_lib(PLAN_VAR_LIB_PATH, [(os.path.join(_CSRC, "plan_var_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []),
                                            f"plan_var_family_{k}.o") for k in range(N_PLANT_FAMILIES)], force, verbose, False)
+
+
+REWARD_DEFER_LIB_PATH = os.path.join(_CSRC, "libdialdefer.so")
+
+
+def build_reward_defer(force: bool = False, verbose: bool = False) -> str:
+    """libdialdefer.so: the Go2's plain-grid rollout kernel that evaluates the walking task's step rewards once per rollout
+    (csrc/reward_defer_kernel.h, one unit: reward_defer.hip, the product flags), a library of its own so that the code objects of
+    libdialhip.so stay as shipped.  libdialhip.so loads it from its own directory when a context that can use it is created; without
+    it such a context runs the per-step kernel (Context.debug_last_launch()["defer_reward"] says which)."""
+    return _build_lib(REWARD_DEFER_LIB_PATH, [(os.path.join(_CSRC, "reward_defer.hip"), [], "reward_defer.o")], force, verbose, False)
 
 
 PLAN_ENS_LIB_PATH = os.path.join(_CSRC, "libdialplanens.so")
@@ -959,14 +973,16 @@ class Context:
         self._check(self.lib.dial_set_state_trace(self.h, _ptr(self._trace), int(rows)), "dial_set_state_trace")
         return self._trace
 
-    LAUNCH_FIELDS = ("inst", "wpb", "blocks", "queue", "relay", "mean_inline", "slice_pieces", "split", "pair", "trace", "con_cap", "rollouts")
+    LAUNCH_FIELDS = ("inst", "wpb", "blocks", "queue", "relay", "mean_inline", "slice_pieces", "split", "pair", "trace", "con_cap", "rollouts",
+                     "defer_reward")
 
     def debug_last_launch(self) -> dict:
         """What this context's most recent rollout launch did (dial_debug_last_launch; tests assert the path they target): kernel
         instantiation `inst` (0 = the capacity-dimension kernel, DimsMax), wavefronts per workgroup, grid workgroups (0: the call returned
         before launching), and 0 / 1 or counts for the rollout queue, the mean-trajectory relay, the interleaved mean trajectory, the
         time-slice pieces, the split launch, the Go2 pair kernel, the state-trace instantiation; `con_cap` the overflow cap in effect
-        (0: no overflow areas), `rollouts` the batch."""
+        (0: no overflow areas), `rollouts` the batch, `defer_reward` 1 when the Go2 walk's kernel that evaluates the step rewards once per
+        rollout ran (dial_options.no_defer_reward)."""
         buf = (ctypes.c_int * len(self.LAUNCH_FIELDS))()
         n = self.lib.dial_debug_last_launch(self.h, buf, len(buf))
         if n != len(self.LAUNCH_FIELDS):

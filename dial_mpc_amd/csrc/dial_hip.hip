@@ -29,6 +29,7 @@
 #include "plan_var_kernel.h"
 #include "plan_ens_kernel.h"
 #include "plugin_ops.h"
+#include "reward_defer_kernel.h"
 
 // the kernels are compiled in their own translation units, one per robot family (kern_family.hip, built in parallel)
 #define DIAL_X(D, WPB, OCC, Q, TR) \
@@ -341,7 +342,7 @@ extern "C" __global__ void __launch_bounds__(64) selftest_kernel(float* out) {
 // ------------------------------------------------------------------ host side
 // dial_debug_last_launch: what the context's most recent rollout launch did, one int per field (tests assert the path they target)
 enum LaunchField { LF_INST, LF_WPB, LF_BLOCKS, LF_QUEUE, LF_RELAY, LF_MEAN_INLINE, LF_SLICE_PIECES, LF_SPLIT, LF_PAIR, LF_TRACE, LF_CON_CAP,
-                   LF_ROLLOUTS, DIAL_LAUNCH_FIELDS };
+                   LF_ROLLOUTS, LF_DEFER_REWARD, DIAL_LAUNCH_FIELDS };
 
 struct dial_ctx {
   int device = 0;
@@ -422,6 +423,11 @@ struct dial_ctx {
   int debug_stall_piece1 = 0;  // DIAL_DEBUG_RELAY_STALL=k (tests): relay piece k - 1 never hands over
   int relay_steps = 3;         // control steps per relay piece (measured: 1 -> no gain, 2 -4.9 %, 3 -5.3 %, 4 -5.0 %, 6 -4.0 %)
   int resident_blocks = 0, resident_blocks_large = 0;   // workgroups of the rollout kernel the whole chip holds at once
+  // Go2 walk, deferred step rewards (reward_defer_kernel.h): the kernel's table, LDS of that launch -- lds_rollout + the stash of T rows --
+  // and how many of its workgroups the chip keeps resident; 0: the context never launches it (dial_create decides, see there)
+  const dial_reward_defer_ops* defer_ops = nullptr;
+  size_t lds_defer = 0;
+  int resident_defer = 0;
   // Go2, two rollouts per wavefront (rollout_kernel2): LDS of the one-wavefront / DIAL_GO2_PAIR_WPB-wavefront workgroups and how
   // many of each the chip keeps resident; pair_ok: the context launches them (dial_options::pair_mode)
   bool pair_ok = false;
@@ -439,6 +445,40 @@ struct dial_ctx {
 };
 
 static thread_local std::string g_err;   // last error of calls that have no context (per calling thread)
+
+// libdialdefer.so (reward_defer.hip): the Go2's rollout kernel that evaluates the step rewards once per rollout, looked up in this
+// library's own directory the first time a context that can use it is created; the IEEE measurement variant links the unit itself.
+// nullptr: no such file, or one built from other sources -- contexts then launch rollout_kernel (its reward lane in every step) and
+// dial_debug_last_launch reports defer_reward = 0.
+#ifdef DIAL_IEEE_BUILD
+extern "C" const dial_reward_defer_ops* dial_reward_defer_ops_v1(void);
+static const dial_reward_defer_ops* reward_defer_load() { return dial_reward_defer_ops_v1(); }
+#else
+static const dial_reward_defer_ops* reward_defer_load() {
+  std::string dir = ".";
+  Dl_info info;
+  if (dladdr((const void*)&reward_defer_load, &info) && info.dli_fname) {
+    dir = info.dli_fname;
+    const size_t slash = dir.rfind('/');
+    dir = slash == std::string::npos ? "." : dir.substr(0, slash);
+  }
+  const std::string path = dir + "/libdialdefer.so";
+  void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);   // (never dlclose'd: the runtime holds its code objects)
+  if (!h) return nullptr;
+  dial_reward_defer_entry entry = (dial_reward_defer_entry)dlsym(h, DIAL_REWARD_DEFER_SYMBOL);
+  return entry ? entry() : nullptr;
+}
+#endif
+static const dial_reward_defer_ops* reward_defer_ops() {
+  static const dial_reward_defer_ops* const ops = [] {   // (once per process, thread-safe initialisation)
+    const dial_reward_defer_ops* o = reward_defer_load();
+    if (o && (o->abi_version != DIAL_REWARD_DEFER_ABI_VERSION || o->sizeof_task != sizeof(dial_task) || o->sizeof_cfg != sizeof(dial_cfg) ||
+              o->sizeof_io != sizeof(dial::RolloutIO) || o->cmodel_bytes != sizeof(CModel<DimsGo2>) || !o->launch || !o->occupancy))
+      o = nullptr;
+    return o;
+  }();
+  return ops;
+}
 
 static int fail(dial_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg;
@@ -955,6 +995,27 @@ static int create_impl(dial_ctx** out, const dial_model* model, const dial_task*
       if (e == hipSuccess) ctx->resident_pair_large = nb * prop.multiProcessorCount;
       if (e == hipSuccess && (ctx->resident_pair <= 0 || ctx->resident_pair_large <= 0)) ctx->pair_ok = false;
     }
+    // Go2 walk: the step rewards once per rollout (reward_defer_kernel.h).  That launch carries a stash of T x DIAL_REWARD_STASH_W
+    // words of dynamic LDS behind the workspace; it exists only where the workgroup still fits NINE per CU (the budget the contact cap
+    // above is sized for: 2049 rollouts resident at once; T = 17: 16 160 + 1 632 B of 17 920, T = 19 is over) and where the position
+    // stage's stores are the words the reward reads: the task's torso and upright body are the trunk (body 1), its feet sites the
+    // four calves' (sites 1 .. 4, in any order).  launch_rollout then takes it for every plain-grid launch the resident set covers.
+    if (e == hipSuccess && ctx->inst == 1 && cfg && !opt.no_defer_reward && task->kind == DIAL_TASK_GO2_WALK) {
+#ifdef DIAL_PROFILE
+      const size_t prof_bytes = 16 + 32 * sizeof(unsigned long long);   // (a profiling build's counters do not count: it measures one workgroup)
+#else
+      const size_t prof_bytes = 0;
+#endif
+      const size_t stash = (size_t)(cfg->Hsample + 1) * DIAL_REWARD_STASH_W * sizeof(float), budget = (size_t)(160 * 1024) / 9 / 512 * 512;
+      bool geom = task->torso_x == 0 && task->upright_x == 0 && task->nfeet == 4;
+      for (int f = 0; f < 4; f++) geom = geom && task->feet_site[f] >= 1 && task->feet_site[f] <= 4;
+      const dial_reward_defer_ops* ops = nullptr;   // (T >= 2: the stash's layout fits its 24 words per step, rollout_body.h)
+      if (geom && cfg->Hsample + 1 >= 2 && ctx->lds_rollout % 16 == 0 && ctx->lds_rollout - prof_bytes + stash <= budget) ops = reward_defer_ops();
+      if (ops) {
+        e = ops->occupancy(&nb, ctx->lds_rollout + stash);
+        if (e == hipSuccess && nb > 0) { ctx->defer_ops = ops; ctx->lds_defer = ctx->lds_rollout + stash; ctx->resident_defer = nb * prop.multiProcessorCount; }
+      }
+    }
     if (e != hipSuccess) { dial_destroy(ctx); return fail(nullptr, DIAL_ERR_HIP, std::string("dial_create: occupancy query: ") + hipGetErrorString(e)); }
     if (opt.no_queue) ctx->resident_blocks = ctx->resident_blocks_large = 0;   // options: one wavefront per rollout at any batch size
     HIP_TRY_CREATE(hipMalloc(&ctx->next, sizeof(int)));
@@ -1301,6 +1362,10 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
   }
   ll[LF_WPB] = wpb; ll[LF_BLOCKS] = blocks; ll[LF_QUEUE] = next != nullptr; ll[LF_RELAY] = relay; ll[LF_MEAN_INLINE] = io.mean_inline;
   ll[LF_SLICE_PIECES] = io.slice_pieces; ll[LF_TRACE] = tracing; ll[LF_CON_CAP] = io.con_cap;
+  // Go2 walk on the plain grid (relay pieces included; rollouts from given controls too): the kernel that evaluates the step rewards
+  // once per rollout, wherever the resident set of its larger workgroups still covers the grid (a relay piece spins for its predecessor)
+  const bool defer = ctx->inst == 1 && !large && !tracing && !next && ctx->defer_ops && blocks <= ctx->resident_defer;
+  ll[LF_DEFER_REWARD] = defer;
   // Batch = 8 x CUs + 1 (N = 2048 on 256 CUs) with multi-wavefront workgroups: the N noisy rollouts as evenly sized
   // workgroups that load every CU with 8 wavefronts (Allegro: one workgroup of 8, H1: two of 4, one wavefront per SIMD
   // each), the mean trajectory as a one-wavefront workgroup launched on the side stream (fork / join by events)
@@ -1353,6 +1418,8 @@ static int launch_rollout(dial_ctx* ctx, const dial::RolloutIO& io_in, int B, hi
     hipLaunchKernelGGL((rollout_kernel<DimsGo2, DIAL_GO2_WPB_LARGE, DIAL_GO2_OCC_LARGE, true>), dim3(blocks),
                        dim3(64 * DIAL_GO2_WPB_LARGE), ctx->lds_large, st, (const CModel<DimsGo2>*)ctx->dcm, (const dial_task*)ctx->dtask,
                        (const dial_cfg*)ctx->dcfg, io, B, ctx->ws_words, next);
+  else if (defer)
+    HIP_TRY(ctx, ctx->defer_ops->launch(blocks, ctx->lds_defer, st, ctx->dcm, (const dial_task*)ctx->dtask, (const dial_cfg*)ctx->dcfg, &io, B, ctx->ws_words));
   else if (ctx->inst == 1) DIAL_LAUNCH_ROLLOUT_Q(DimsGo2, 1, false);
   else if (ctx->inst == 2) DIAL_LAUNCH_ROLLOUT(DimsH1, 3);
   else if (ctx->inst == 3) DIAL_LAUNCH_ROLLOUT(DimsH1Loco, 2);

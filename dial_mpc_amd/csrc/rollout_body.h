@@ -1809,7 +1809,57 @@ DIAL_DEV float gait_ztar(const M* m, int f, float step) {
 // PRE (rollouts of the Dims::pre_ctrl instantiations): the joint targets and the gait clock of control step `st` come from the
 // rollout's tables (Ws::jtab / ztab, built in its prologue: rollout_driver.h), and the step's outputs are stored by the phases that
 // produce them (Wave::out_io / out_row: x.pos by the position stage, q / qd by the integrator, the reward by its lane).
-template <bool FULL_INFO, bool PRE = false, class W, class M>
+// ---- deferred step rewards (wave.h: WaveD -- the Go2 walk's plain-grid launches, reward_defer_kernel.h)
+// Nothing of the physics reads a step reward.  So per step the position stage stores the words the walking reward reads of the
+// forward quantities (smooth_quad.h: lane 0 and the calf lanes hold them in registers) to the step's rows of a stash in LDS, what is
+// left of the reward phase is reward_step_deferred, and after the last step of the rollout (piece) env_step<.., EPI = true> runs the
+// reward phase once, control step st + k in lane k, each lane on a VIEW of the workspace whose kinematic arrays point into its step's
+// rows: the terms' code is the reward lane's, not a copy.  forward() computes xquat / xpos / com / cvel / spos from the state the
+// step starts from, nothing after the position stage rewrites them and euler() rewrites qvel and qpos only, so the stored words are
+// the ones the step's reward lane reads (tests/test_reward_defer_emu.py: bit for bit).
+// Stash: T rows of 16 words -- trunk quaternion (4), position (3), root com (3), cvel (6) -- then one block of 12 words per three
+// steps with the foot-site heights at the stride the terms index spos with: step t's site 1 + r at (t % 3) + 3 r.  16 T + 12 ceil(T / 3)
+// words, inside the DIAL_REWARD_STASH_W words per step the launch provides (T >= 2).  The launch defers only where the task's torso
+// and upright body are the trunk (body 1) and its feet sites are the calves' (sites 1 .. 4): dial_hip.hip, dial_create.
+#define DIAL_REWARD_STASH_W 24
+template <class W>
+DIAL_DEV void reward_rows(W& w, int st) {
+  w.srow = w.stash + 16 * st;
+  w.zrow = w.zbase + 12 * (st / 3) + st % 3;
+}
+template <class W, class M>
+DIAL_DEV Ws reward_view(const W& w, const M* m, const Ws& s, int st) {
+  const int tb = m->torso_x + 1;
+  float* const row = w.stash + 16 * st;
+  Ws v = s;
+  v.xquat = row - 4 * tb;
+  v.xpos = row + 4 - 3 * tb;
+  v.com = row + 7 - 3 * m->body_rootid[tb];
+  v.cvel = row + 10 - 6 * tb;
+  v.spos = w.zbase + 12 * (st / 3) + st % 3 - 5;   // (site 1's z, spos[3 * 1 + 2], is the block's first word of this step)
+  return v;
+}
+// what is left of the reward phase in a step that defers: lane 0 advances the step counter, lanes 1 .. nq store the step's q row
+template <class W, class M>
+DIAL_DEV void reward_step_deferred(W& w, const M* m, const Ws& s) {
+  const int nq = dim_nq(m);
+  // (an opaque lane id: hoisted out of the T-step loop, the lanes' 64-bit addresses into the q row were two spilled VGPRs)
+  DIAL_LANE_SCOPE(w);
+  w.items(1 + nq, [&](int it) {
+    if (it == 0) s.info[DIAL_INFO_STEP] += 1.f;
+    else if (w.out_io && w.out_io->qss) w.out_io->qss[(size_t)w.out_row * nq + (it - 1)] = s.qpos[it - 1];
+  });
+}
+
+template <bool EPI, class W>
+DIAL_DEV int reward_items(const W& w, int n) {   // lanes of the reward phase: n, or (EPI) one per control step
+  if constexpr (EPI) return w.epi_cnt;
+  else return n;
+}
+
+// EPI (WaveD only): no physics frame -- the reward phase alone, for the w.epi_cnt control steps from `st` on, step st + k in lane k (see above);
+// lane k leaves its step reward in the first word of its row of the stash, for the caller's ordered sum.
+template <bool FULL_INFO, bool PRE = false, bool EPI = false, class W, class M>
 DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int st = 0) {
   const int nu = dim_nu(m);
   const bool walk = m->kind == DIAL_TASK_GO2_WALK || m->kind == DIAL_TASK_H1_WALK || m->kind == DIAL_TASK_H1_LOCO ||
@@ -1848,7 +1898,7 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
     }
   });
   DIAL_MARK(w, 25);
-  const int n_frames = PRE ? 1 : m->n_frames;   // (Dims::pre_ctrl: one physics step per control step, dial_create checks)
+  const int n_frames = EPI ? 0 : (PRE ? 1 : m->n_frames);   // (Dims::pre_ctrl: one physics step per control step, dial_create checks; EPI: none)
   for (int f = 0; f < n_frames; f++) {  // pipeline_step
 #ifndef DIAL_EMU
     if (w.launder) { asm volatile("" : "+v"(w.lane)); w.lane_r = w.lane; }   // see rollout_driver.h: the step loop
@@ -1940,6 +1990,19 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
       return s.info[DIAL_INFO_REWARD];
     }
   }
+  if constexpr (W::defer_rewards && !EPI) {
+    static_assert(PRE && !FULL_INFO && !M::D::user, "deferred rewards: rollouts of the Go2's own instantiation");
+    reward_step_deferred(w, m, s);
+    DIAL_MARK(w, 10);
+    return 0.f;
+  }
+  // the workspace the terms read the forward quantities from and their control step: the step's own -- or, EPI, the lane's view / step
+  Ws rv;
+  if constexpr (EPI) rv = s;
+  const Ws& rvc = rv;
+  const Ws& rs = EPI ? rvc : s;
+  int rst_epi = st;
+  const int& rst = EPI ? rst_epi : st;
   // ---- reward terms (all read the PRE-integration forward quantities)
   //   0 gaits | contact   1 upright   2 yaw   3 vel (walk) | pos (jump)   4 ang_vel | penalty   5 height   6 energy   7 done
   // The terms are independent scalar chains.  One term per lane sounds parallel but is not: lanes that take different
@@ -1962,12 +2025,12 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
       const float step = info[DIAL_INFO_STEP];
       // torso / upright-body state, fetched once up front by every term lane (same addresses: LDS broadcasts, one
       // round trip) instead of inside the divergent branches, where each term would pay its own dependent fetch
-      const float tq[4] = {s.xquat[4 * tb], s.xquat[4 * tb + 1], s.xquat[4 * tb + 2], s.xquat[4 * tb + 3]};
-      const float uq[4] = {s.xquat[4 * ub], s.xquat[4 * ub + 1], s.xquat[4 * ub + 2], s.xquat[4 * ub + 3]};
-      const float tp[3] = {s.xpos[3 * tb], s.xpos[3 * tb + 1], s.xpos[3 * tb + 2]};
-      const float* cmr = s.com + 3 * m->body_rootid[tb];
+      const float tq[4] = {rs.xquat[4 * tb], rs.xquat[4 * tb + 1], rs.xquat[4 * tb + 2], rs.xquat[4 * tb + 3]};
+      const float uq[4] = {rs.xquat[4 * ub], rs.xquat[4 * ub + 1], rs.xquat[4 * ub + 2], rs.xquat[4 * ub + 3]};
+      const float tp[3] = {rs.xpos[3 * tb], rs.xpos[3 * tb + 1], rs.xpos[3 * tb + 2]};
+      const float* cmr = rs.com + 3 * m->body_rootid[tb];
       const float tcom[3] = {cmr[0], cmr[1], cmr[2]};
-      const float tv[6] = {s.cvel[6 * tb], s.cvel[6 * tb + 1], s.cvel[6 * tb + 2], s.cvel[6 * tb + 3], s.cvel[6 * tb + 4], s.cvel[6 * tb + 5]};
+      const float tv[6] = {rs.cvel[6 * tb], rs.cvel[6 * tb + 1], rs.cvel[6 * tb + 2], rs.cvel[6 * tb + 3], rs.cvel[6 * tb + 4], rs.cvel[6 * tb + 5]};
       const float yaw_tar0 = info[DIAL_INFO_YAW_TAR], pos_tar_z = info[DIAL_INFO_POS_TAR + 2];
       float out = 0.f;
       if (it == 0) {
@@ -1975,7 +2038,7 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
           float reward_gaits = 0.f;
   #pragma unroll
           for (int f = 0; f < NF; f++) {
-            const float z_tar = PRE ? s.ztab[st * DIAL_ZTAB_W + f] : s.ztar[f], zs = s.spos[3 * m->feet_site[f] + 2];   // (PRE: the rollout's gait-clock table)
+            const float z_tar = PRE ? s.ztab[rst * DIAL_ZTAB_W + f] : s.ztar[f], zs = rs.spos[3 * m->feet_site[f] + 2];   // (PRE: the rollout's gait-clock table)
             float fz;
             if (kind == DIAL_TASK_GO2_WALK) {
               float e = (z_tar - zs) / 0.05f;
@@ -2029,7 +2092,7 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
         const float yaw = quat_yaw(rot_t);
         if (walk) {
           float yaw_tar;
-          if constexpr (PRE) yaw_tar = s.ztab[st * DIAL_ZTAB_W + DIAL_MAX_FEET + 3];   // (the rollout's table of ramped targets)
+          if constexpr (PRE) yaw_tar = s.ztab[rst * DIAL_ZTAB_W + DIAL_MAX_FEET + 3];   // (the rollout's table of ramped targets)
           else {
             const float a2 = cmd[5];
             const float avt = dm::fminf_(a2 * step * dt / m->ramp_up_time, a2);
@@ -2055,7 +2118,7 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
             dm::inv_rotate(vb, vel, rot_t);
             float vt[2];
             for (int k = 0; k < 2; k++) {
-              if constexpr (PRE) vt[k] = s.ztab[st * DIAL_ZTAB_W + DIAL_MAX_FEET + k];
+              if constexpr (PRE) vt[k] = s.ztab[rst * DIAL_ZTAB_W + DIAL_MAX_FEET + k];
               else { const float v = cmd[k]; vt[k] = dm::fminf_(v * step * dt / m->ramp_up_time, v); }
             }
             const float e0 = vb[0] - vt[0], e1 = vb[1] - vt[1];
@@ -2073,7 +2136,7 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
               out = -e3;
             } else {
               float avt;
-              if constexpr (PRE) avt = s.ztab[st * DIAL_ZTAB_W + DIAL_MAX_FEET + 2];
+              if constexpr (PRE) avt = s.ztab[rst * DIAL_ZTAB_W + DIAL_MAX_FEET + 2];
               else { const float a2 = cmd[5]; avt = dm::fminf_(a2 * step * dt / m->ramp_up_time, a2); }
               const float ea = ab[2] - avt;
               out = -(ea * ea);
@@ -2127,9 +2190,13 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
     };
     // ---- terms, total in the reference's summation order and info update (one lane; last_ctrl by nu lanes)
     // (PRE: lanes 1 .. nq also store this step's q row -- the integrator's results, one element per lane)
-    w.items(1 + (PRE ? dim_nq(m) : nu), [&](int it) {
+    w.items(reward_items<EPI>(w, 1 + (PRE ? dim_nq(m) : nu)), [&](int it) {
       float* info = s.info;
-      if (it > 0) {
+      if constexpr (EPI) {   // this lane's control step and its view of the workspace
+        rst_epi = st + it;
+        rv = reward_view(w, m, s, rst_epi);
+      }
+      if (!EPI && it > 0) {
         if (!walk && it <= nu) info[DIAL_INFO_LAST_CTRL + it - 1] = s.ctrl[it - 1];
         if constexpr (PRE) { if (w.out_io && w.out_io->qss) w.out_io->qss[(size_t)w.out_row * dim_nq(m) + (it - 1)] = s.qpos[it - 1]; }
         return;
@@ -2169,6 +2236,11 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
           info[DIAL_INFO_VEL_TAR + k] = dm::fminf_(v * step * dt / m->ramp_up_time, v);
           info[DIAL_INFO_ANG_VEL_TAR + k] = dm::fminf_(a * step * dt / m->ramp_up_time, a);
         }
+      }
+      if constexpr (EPI) {   // (the steps advanced the counter themselves; the reward goes to the caller's ordered sum and to rewss)
+        w.stash[16 * rst] = reward;
+        if (w.out_io && w.out_io->rewss) w.out_io->rewss[w.out_row + it] = reward;
+        return;
       }
       if (FULL_INFO) info[DIAL_INFO_DONE] = r[7];
       info[DIAL_INFO_STEP] = step + 1.f;

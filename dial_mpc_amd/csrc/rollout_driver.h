@@ -97,6 +97,10 @@ DIAL_DEV double load_sum(const float* p) {
 // advances one step per step of everybody else and ends with them: a batch of k x slots + 1 rollouts takes k rounds and one
 // STEP instead of k rounds and one lone ROLLOUT (Go2, N = 4096: 0.78 ms as a queue item).  Bit-identical: the same steps on
 // the same states.
+// W::defer_rewards (wave.h: WaveD, the wave of reward_defer_kernel.h -- launched for the Go2 walk only, never with `helper`): the
+// step rewards are evaluated once per rollout (piece).  Every step stores what its reward reads to the stash (smooth_quad.h); after the
+// last step lane k evaluates step st_begin + k with the reward phase's own code (rollout_body.h: env_step<.., EPI>), stores it to rewss,
+// and the steps enter the fp64 sum in ascending step order.  T - 1 of the T one-lane reward phases leave the dependence chain.
 template <bool TRACE = false, class W, class M>
 DIAL_DEV void rollout_sample(W& w, const M* m, const dial_task* tg, const dial_cfg* cfg, const Ws& s,
                              const RolloutIO& io, int n, int relay = -1, int helper = -1, bool init_ws = true) {
@@ -334,8 +338,10 @@ DIAL_DEV void rollout_sample(W& w, const M* m, const dial_task* tg, const dial_c
     DIAL_MARK(w, 11);
     const int work0 = w.work;
     if constexpr (PRE) { w.out_io = &io; w.out_row = row * T + st; }   // (the step's outputs are stored by the phases that produce them)
+    if constexpr (W::defer_rewards) reward_rows(w, st);
     float rew = env_step<false, PRE>(w, m, tg, s, st);
-    if (mean_now) msum += (rsum_t)rew; else rsum += (rsum_t)rew;
+    if (mean_now) msum += (rsum_t)rew;
+    else if constexpr (!W::defer_rewards) rsum += (rsum_t)rew;
 #ifndef DIAL_EMU
     if constexpr (M::D::ell) {
       if (io.work_stat && relay < 0) {   // once per control step: add own work to the launch totals, compare rates, set the level
@@ -438,6 +444,16 @@ DIAL_DEV void rollout_sample(W& w, const M* m, const dial_task* tg, const dial_c
       mean_now = ok;   // (!ok: the predecessor never came -- the own rollout resumes, its state is still in the workspace)
     }
 #endif
+  }
+  if constexpr (W::defer_rewards) {
+    static_assert(!TRACE && PRE, "deferred rewards: the Go2's plain-grid rollouts");
+    // (an opaque lane id: the lanes' stash addresses stay inside this scope, nothing of them is hoisted across the T-step loop)
+    DIAL_LANE_SCOPE(w);
+    w.epi_cnt = st_end - st_begin;
+    w.out_io = &io;
+    w.out_row = n * T + st_begin;
+    env_step<false, PRE, true>(w, m, tg, s, st_begin);
+    for (int k = st_begin; k < st_end; k++) rsum += (rsum_t)w.stash[16 * k];   // ascending step order: the sum rounds as the per-step one
   }
 #ifdef DIAL_PROFILE
   DIAL_MARK(w, 11);

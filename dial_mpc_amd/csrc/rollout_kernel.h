@@ -11,6 +11,9 @@
 // WPB wavefronts (= samples) per workgroup share ONE staged copy of the constants; each wavefront has
 // its own workspace.  WPB is chosen per robot so that N+1 = 2049 wavefronts are co-resident (>= 9 per CU):
 // Go2 1 (16 KB/wave), H1 3 (10 KB constants + 3 x 13.7 KB: 3 workgroups = 9 wavefronts per CU), H1 loco 2, generic 1.
+// LDS per workgroup = the staged constants + WPB workspaces (+ the profiling counters of a DIAL_PROFILE build); the Go2's
+// deferred-reward launch (reward_defer_kernel.h) adds T x 24 words of reward stash behind them: 7 232 + 8 928 + 1 632 B at T = 17,
+// inside the 17 920 B that keep nine workgroups on a CU.
 // This is the only workgroup-level barrier of the kernel (phase boundaries are
 // wavefront-scope fences, wave.h).
 template <class D, int WPB = 1>

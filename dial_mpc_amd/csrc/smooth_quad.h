@@ -283,6 +283,16 @@ DIAL_DEV void forward_smooth_quad(W& w, const M* m, const Ws& s) {
       for (int k = 0; k < 4; k++) s.qpos[3 + k] = tquat[k];   // (kinematics normalises the free joint's quaternion in place)
     }
     if (d == 3) for (int k = 0; k < 3; k++) s.spos[3 * (1 + r) + k] = lane_val(F[16 + k], l);
+    if constexpr (W::defer_rewards) {
+      // deferred step rewards (wave.h: WaveD; rollout_body.h: reward_view): what this step's reward reads, to the step's rows of the stash
+      if (l == 0) {
+        store4(w.srow, lane_val(PL[3], l), lane_val(PL[4], l), lane_val(PL[5], l), lane_val(PL[6], l));
+        store4(w.srow + 4, lane_val(PL[0], l), lane_val(PL[1], l), lane_val(PL[2], l), com[0]);
+        store4(w.srow + 8, com[1], com[2], lane_val(VA[0], l), lane_val(VA[1], l));
+        store4(w.srow + 12, lane_val(VA[2], l), lane_val(VA[3], l), lane_val(VA[4], l), lane_val(VA[5], l));
+      }
+      if (d == 3) w.zrow[3 * r] = lane_val(F[18], l);
+    }
     if constexpr (!FUSED) {   // packed M: the structural zeros (the dof lanes below write the tree's entries only)
       for (int e = l; e < M::D::NTRI; e += 64) s.M[e] = 0.f;
     }

@@ -86,6 +86,7 @@ inline float emu_tree32(const float* v) {     // half-wave sum (WaveH): the two 
 #define DIAL_LANE_SCOPE_IF(cond, w)
 struct Wave {
   static constexpr bool half2 = false;   // (WaveH below: two samples per wavefront, this object is one 32-lane half)
+  static constexpr bool defer_rewards = false;   // (WaveD below)
   bool tree_sums = false;                // wave sums in the GPU's association (see emu_row_tree)
   bool launder = false;   // (GPU only: opaque lane id per step, see the HIP Wave)
   // the control step's rows of the launch's output tensors, for the phases that store what they produce (Dims::pre_ctrl)
@@ -285,6 +286,15 @@ struct Wave {
   template <int K>
   vfloat rcp_pick(const vfloat& X, const vfloat& Y) { return vrcp(pick<K>(X, Y)); }
 };
+// WaveD: the wave that defers the Go2 walk's step rewards (see the HIP section)
+struct WaveD : Wave {
+  static constexpr bool defer_rewards = true;
+  float* stash = nullptr;
+  float* srow = nullptr;
+  float* zrow = nullptr;
+  float* zbase = nullptr;   // the height blocks, behind the T rows
+  int epi_cnt = 0;
+};
 
 // ---- WaveH: TWO samples per wavefront, one per 32-lane half (HIP section below).  The emulator runs ONE half: logical lanes
 // 0..31 (lanes 32..63 of a vfloat mirror them), so that the 32-lane layouts of smooth_quad2.h / solver_reg2.h can be compared
@@ -429,6 +439,7 @@ struct LaneScopeIf<true, W> : LaneScope<W> {
 #endif
 struct Wave {
   static constexpr bool half2 = false;   // (WaveH below: two samples per wavefront)
+  static constexpr bool defer_rewards = false;   // (WaveD below: the step rewards once per rollout)
   int lane;
   // The control step's rows of the launch's output tensors (row = rollout x T + step), for the phases that store what they
   // produce (Dims::pre_ctrl; rollout_driver.h sets them before env_step): one kernarg pointer + one index, not four row pointers
@@ -729,6 +740,19 @@ struct Wave {
   template <int K>
   __device__ __forceinline__ vfloat rcp_pick(vfloat X, vfloat Y) { return vrcp(pick<K>(X, Y)); }
 #endif
+};
+// WaveD: the wave of the ONE kernel that defers the Go2 walk's step rewards (reward_defer_kernel.h; rollout_body.h: reward_view).
+// `stash`: T x DIAL_REWARD_STASH_W words of LDS behind the workspace, provided by that launch.  Per control step the position stage
+// stores what the step's reward reads to `srow` (16 words: trunk quaternion, position, root com, cvel) and the calf lanes the heights
+// of their foot sites to `zrow` (stride 3); at the end of the rollout (piece) lane k evaluates step st_begin + k, k < `epi_cnt`.
+// A type of its own, not fields of Wave: every other kernel compiles exactly what it compiled before.
+struct WaveD : Wave {
+  static constexpr bool defer_rewards = true;
+  float* stash = nullptr;
+  float* srow = nullptr;
+  float* zrow = nullptr;
+  float* zbase = nullptr;   // the height blocks, behind the T rows
+  int epi_cnt = 0;
 };
 
 // ---- WaveH: TWO samples per wavefront.  Each 32-lane half owns one sample; the kernel body is the same per-lane program,

@@ -385,6 +385,13 @@ typedef struct dial_options {
                                  other side of 2304 (N = 4096 over 2 or 4 ranks) equals the fused run at rounding level, not bit for
                                  bit; ranks of one run always agree with each other (same shard size).  pair_mode 1 or 2 on every
                                  context restores bit-equality across shardings.                                                  */
+  int32_t no_defer_reward;    /* 1: the Go2 walk's plain-grid rollouts evaluate every step's reward in the step, on one lane (the kernel
+                                 every other launch shape runs).  Default: once per rollout, control step t in lane t, from T x 24 words
+                                 of LDS the launch adds behind the workspace -- wherever the workgroup still fits nine per CU (T <= 17 for
+                                 the Go2) and the resident set covers the grid; dial_debug_last_launch reports which one ran
+                                 (defer_reward).  The same term code on the same input bits and the same ordered fp64 sum: rewards
+                                 bit-identical on the build without contraction and, as measured, on the product build.
+                                 (Declared before plan_cap, which stays the struct's last field.)                                 */
   int32_t plan_cap;           /* plans one dial_reverse_once_batch[_rng] call may carry, 0 .. DIAL_MAX_PLANS (0 = 1): the rollout scratch,
                                  the weights and K4b's partial sums are sized for plan_cap x (Nsample + 1) rollouts.  0 / 1 allocate exactly
                                  what a context without grouped plans needs.                                                       */

@@ -16,6 +16,11 @@
 template __global__ void rollout_kernel<PROBE_D, PROBE_WPB, PROBE_OCC, PROBE_QUEUE>(const CModel<PROBE_D>*, const dial_task*, const dial_cfg*,
                                                                                     dial::RolloutIO, int, int, int*);
 
+#ifdef PROBE_DEFER   // the Go2's deferred-reward kernel as well: tools/isa/probe.sh DimsGo2 1 3 false -DPROBE_DEFER
+#include "../../dial_mpc_amd/csrc/reward_defer_kernel.h"
+template __global__ void rollout_defer_kernel<DimsGo2>(const CModel<DimsGo2>*, const dial_task*, const dial_cfg*, dial::RolloutIO, int, int);
+#endif
+
 #ifdef PROBE_PAIR
 template __global__ void rollout_kernel2<PROBE_D, PROBE_WPB, PROBE_OCC, PROBE_QUEUE>(const CModel<PROBE_D>*, const dial_task*, const dial_cfg*,
                                                                                      dial::RolloutIO, int, int, int*);
