@@ -1137,6 +1137,7 @@ DIAL_DEV void forward(W& w, const M* m, const Ws& s) {
   } else
   if constexpr (kQuadDims<typename M::D>) {   // quadruped topology: the whole position / velocity stage in registers (smooth_quad.h)
     forward_smooth_quad(w, m, s);
+    if constexpr (W::lean_tail_cut) { if (w.tail_cut) return; }   // (a lean rollout's last step: nothing reads the solve, wave.h)
     forward_constraints(w, m, s, nca, nea);
     return;
   }
@@ -1904,6 +1905,11 @@ DIAL_DEV float env_step(W& w, const M* m, const dial_task* tg, const Ws& s, int 
     if (w.launder) { asm volatile("" : "+v"(w.lane)); w.lane_r = w.lane; }   // see rollout_driver.h: the step loop
 #endif
     forward(w, m, s);
+    if constexpr (W::lean_tail_cut) {
+      // the last step of a lean rollout (rollout_driver.h sets w.tail_cut): nothing reads the integrated state, the step counter or
+      // a q row -- the step's reward is evaluated from the stash rows the position stage stored
+      if (w.tail_cut) { DIAL_MARK(w, 9); return 0.f; }
+    }
     euler(w, m, s);
     DIAL_MARK(w, 9);
   }

@@ -339,6 +339,10 @@ DIAL_DEV void rollout_sample(W& w, const M* m, const dial_task* tg, const dial_c
     const int work0 = w.work;
     if constexpr (PRE) { w.out_io = &io; w.out_row = row * T + st; }   // (the step's outputs are stored by the phases that produce them)
     if constexpr (W::defer_rewards) reward_rows(w, st);
+    // W::lean_tail_cut (wave.h: WaveD): the rollout's last control step -- not a relay piece's, which hands a state on -- of a launch
+    // that stores neither q nor qd ends after the position stage (forward, env_step): the stash rows of its reward and its x row
+    // are stored there, and no step follows that would read the state the rest of the step computes.  Wave-uniform, from scalars.
+    if constexpr (W::lean_tail_cut) w.tail_cut = (st + 1 == T && !io.qss && !io.qdss && helper < 0 && !mean_now) ? 1 : 0;
     float rew = env_step<false, PRE>(w, m, tg, s, st);
     if (mean_now) msum += (rsum_t)rew;
     else if constexpr (!W::defer_rewards) rsum += (rsum_t)rew;

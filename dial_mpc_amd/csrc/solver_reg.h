@@ -288,6 +288,10 @@ DIAL_DEV vfloat reg_chol(W& w, const M* m, const float* A, vfloat bvec, float* s
   else return reg_chol_solve_v<D, TopoT, REUSE>(w, m, A, bvec, scratch, dinv_io);
 }
 
+// host emulator harnesses may count how a solve ends (at_cap: with niter at the iteration cap; otherwise by tolerance); nothing by default
+#ifndef DIAL_SOLVER_EXIT_HOOK
+#define DIAL_SOLVER_EXIT_HOOK(at_cap)
+#endif
 template <class W, class M>
 DIAL_DEV void solver_reg(W& w, const M* m, const Ws& s) {
   constexpr int NV = M::D::NV, NC = M::D::NC, NL = M::D::NL;
@@ -396,16 +400,21 @@ DIAL_DEV void solver_reg(W& w, const M* m, const Ws& s) {
   unsigned long long act_prev = 0;
   vfloat h_dinv = vzero;
   bool h_valid = false;
+#ifdef DIAL_PROFILE
+  // how often does the active set (rows with D > 0 and Jaref < 0) survive from one Newton iteration to the next?  (ja: Jaref at
+  // the top of a pass)
+  const auto prof_active_set = [&](const vfloat& ja) {
+    const unsigned long long cur = __builtin_amdgcn_ballot_w64(vlt0(ja) && (vD > 0.f));
+    static_assert(sizeof(cur) == 8, "");
+    if (niter == 1 && w.lane == 0 && w.acc) { w.acc[28] += 1; if (cur == prof_prev_act) w.acc[29] += 1; }
+    prof_prev_act = cur;
+  };
+#endif
   for (;;) {
     // ---- _update_constraint: forces; _update_gradient: grad = Ma - qfrc_smooth - J^T f
     const vbool act = vlt0(vJa);
 #ifdef DIAL_PROFILE
-    {   // how often does the active set (rows with D > 0 and Jaref < 0) survive from one Newton iteration to the next?
-      const unsigned long long cur = __builtin_amdgcn_ballot_w64(act && (vD > 0.f));
-      static_assert(sizeof(cur) == 8, "");
-      if (niter == 1 && w.lane == 0 && w.acc) { w.acc[28] += 1; if (cur == prof_prev_act) w.acc[29] += 1; }
-      prof_prev_act = cur;
-    }
+    prof_active_set(vJa);
 #endif
     const vfloat vf = vsel(act, vD * (vzero - vJa), vzero);
     vfloat qfc = vls * vf;  // limit row of the own dof
@@ -448,7 +457,7 @@ DIAL_DEV void solver_reg(W& w, const M* m, const Ws& s) {
     } else {
       done = niter >= 1;
     }
-    if (done) break;
+    if (done) { DIAL_SOLVER_EXIT_HOOK(niter > 0 && niter >= max_iter); break; }
 
     // ---- Newton direction: H = M + J^T diag(D*active) J in LDS (lane per entry), Cholesky in registers
     const vfloat vwgt = vsel(act, vD, vzero);
@@ -621,16 +630,37 @@ DIAL_DEV void solver_reg(W& w, const M* m, const Ws& s) {
     }
     float alpha;
     const bool improved = ls_result(p0, lo, hi, alpha);
-    if (improved) {
+    const auto end_pass = [&] {
+      niter++;
+#ifdef DIAL_PROFILE
+      if (w.lane == 0 && w.acc) { w.acc[30] += ls_iter; w.acc[31] += 1; }
+#endif
+      DIAL_MARK(w, 7);
+    };
+    if constexpr (W::solver_cap_exit) {
+      // (wave.h: WaveD) With niter at the cap the next pass could only find `niter >= max_iter`: its forces, J^T f, gradient and
+      // three-way reduction are read by nothing, and after the loop only vqacc is.  So the loop ends here, before that pass and
+      // before the Ma / Jaref updates that only it would read.  Passes with niter == 0 are untouched: max_iter == 0 still ends at the
+      // first `done`, and max_iter == 1 ends here after one iteration, where `done = niter >= 1` ended it one pass later.
+      if (improved) vqacc = vqacc + vsearch * alpha;
+      if (niter + 1 >= max_iter) {
+        end_pass();
+#ifdef DIAL_PROFILE
+        prof_active_set(improved ? vJa + vjv * alpha : vJa);   // (max_iter == 1: the cut pass was the one that counted niter == 1)
+#endif
+        DIAL_SOLVER_EXIT_HOOK(true);
+        break;
+      }
+      if (improved) {
+        vMa = vMa + vmv * alpha;
+        vJa = vJa + vjv * alpha;
+      }
+    } else if (improved) {
       vqacc = vqacc + vsearch * alpha;
       vMa = vMa + vmv * alpha;
       vJa = vJa + vjv * alpha;
     }
-    niter++;
-#ifdef DIAL_PROFILE
-    if (w.lane == 0 && w.acc) { w.acc[30] += ls_iter; w.acc[31] += 1; }
-#endif
-    DIAL_MARK(w, 7);
+    end_pass();
   }
   w.items(NV, [&](int i) {
     const float q = lane_val(vqacc, i);

@@ -26,6 +26,15 @@
 #pragma once
 #include "rollout_io.h"
 
+// A/B switches of WaveD's two work-removal traits (below): 1 restores the full Newton pass past the iteration cap / the complete
+// last step of a lean rollout in the deferring kernel.  Nothing else reads them.
+#ifndef DIAL_DEFER_FULL_SOLVE
+#define DIAL_DEFER_FULL_SOLVE 0
+#endif
+#ifndef DIAL_DEFER_FULL_TAIL
+#define DIAL_DEFER_FULL_TAIL 0
+#endif
+
 #ifdef DIAL_EMU
 #include <cmath>
 #include <cstdio>
@@ -87,6 +96,7 @@ inline float emu_tree32(const float* v) {     // half-wave sum (WaveH): the two 
 struct Wave {
   static constexpr bool half2 = false;   // (WaveH below: two samples per wavefront, this object is one 32-lane half)
   static constexpr bool defer_rewards = false;   // (WaveD below)
+  static constexpr bool solver_cap_exit = false, lean_tail_cut = false;   // (WaveD below)
   bool tree_sums = false;                // wave sums in the GPU's association (see emu_row_tree)
   bool launder = false;   // (GPU only: opaque lane id per step, see the HIP Wave)
   // the control step's rows of the launch's output tensors, for the phases that store what they produce (Dims::pre_ctrl)
@@ -289,6 +299,8 @@ struct Wave {
 // WaveD: the wave that defers the Go2 walk's step rewards (see the HIP section)
 struct WaveD : Wave {
   static constexpr bool defer_rewards = true;
+  static constexpr bool solver_cap_exit = !DIAL_DEFER_FULL_SOLVE, lean_tail_cut = !DIAL_DEFER_FULL_TAIL;
+  int tail_cut = 0;
   float* stash = nullptr;
   float* srow = nullptr;
   float* zrow = nullptr;
@@ -440,6 +452,7 @@ struct LaneScopeIf<true, W> : LaneScope<W> {
 struct Wave {
   static constexpr bool half2 = false;   // (WaveH below: two samples per wavefront)
   static constexpr bool defer_rewards = false;   // (WaveD below: the step rewards once per rollout)
+  static constexpr bool solver_cap_exit = false, lean_tail_cut = false;   // (WaveD below: work no output reads)
   int lane;
   // The control step's rows of the launch's output tensors (row = rollout x T + step), for the phases that store what they
   // produce (Dims::pre_ctrl; rollout_driver.h sets them before env_step): one kernarg pointer + one index, not four row pointers
@@ -746,8 +759,18 @@ struct Wave {
 // stores what the step's reward reads to `srow` (16 words: trunk quaternion, position, root com, cvel) and the calf lanes the heights
 // of their foot sites to `zrow` (stride 3); at the end of the rollout (piece) lane k evaluates step st_begin + k, k < `epi_cnt`.
 // A type of its own, not fields of Wave: every other kernel compiles exactly what it compiled before.
+// Two more traits of this kernel alone, each about work whose results no output reads:
+//   solver_cap_exit: the Newton loop (solver_reg.h) ends as soon as the iteration cap is reached, before the constraint update,
+//     gradient and reductions of a pass that could only find `niter >= max_iter`;
+//   lean_tail_cut: in the LAST control step of a rollout that stores neither q nor qd (`tail_cut`, wave-uniform 0 / 1, set per step by
+//     rollout_driver.h) the step ends after the position stage, whose output phase stores the reward's inputs and the x row; the
+//     constraint solve, the integrator and the step counter would only feed a next step.  (An int, and tested BEHIND the stage: as a
+//     bool the flag cost 4 more spilled SGPRs, and a branch inside the stage -- which would also save its collision / M / bias-force
+//     tail -- cuts the stage's one scheduling region in two: 145 VGPRs instead of 168 and every step 5 % slower, measured.)
 struct WaveD : Wave {
   static constexpr bool defer_rewards = true;
+  static constexpr bool solver_cap_exit = !DIAL_DEFER_FULL_SOLVE, lean_tail_cut = !DIAL_DEFER_FULL_TAIL;
+  int tail_cut = 0;
   float* stash = nullptr;
   float* srow = nullptr;
   float* zrow = nullptr;
