@@ -78,9 +78,12 @@ def build(force: bool = False, verbose: bool = False, ieee: bool = False) -> str
         build_plan_var(force=force, verbose=verbose)
         build_plan_ens(force=force, verbose=verbose)
         build_reward_defer(force=force, verbose=verbose)
-    # (the IEEE measurement variant links the deferred-reward kernel's unit itself: libdialhip_ieee.so's code objects are pinned by nothing)
+        build_update_rule(force=force, verbose=verbose)
+    # (the IEEE measurement variant links the deferred-reward kernel's and the elite rule's units itself: libdialhip_ieee.so's code
+    #  objects are pinned by nothing)
     return _build_lib(IEEE_LIB_PATH if ieee else LIB_PATH, [(os.path.join(_CSRC, "dial_hip.hip"), [], "dial_hip.o")] +
-                      ([(os.path.join(_CSRC, "reward_defer.hip"), [], "reward_defer.o")] if ieee else []) +
+                      ([(os.path.join(_CSRC, "reward_defer.hip"), [], "reward_defer.o"),
+                        (os.path.join(_CSRC, "update_rule.hip"), [], "update_rule.o")] if ieee else []) +
                       [(os.path.join(_CSRC, "kern_family.hip"), [f"-DDIAL_FAMILY={k}"] + _FAMILY_FLAGS.get(k, []), f"kern_family_{k}.o")
                        for k in range(N_FAMILIES)], force, verbose, ieee)
 
@@ -142,6 +145,16 @@ def build_reward_defer(force: bool = False, verbose: bool = False) -> str:
     libdialhip.so stay as shipped.  libdialhip.so loads it from its own directory when a context that can use it is created; without
     it such a context runs the per-step kernel (Context.debug_last_launch()["defer_reward"] says which)."""
     return _build_lib(REWARD_DEFER_LIB_PATH, [(os.path.join(_CSRC, "reward_defer.hip"), [], "reward_defer.o")], force, verbose, False)
+
+
+UPDATE_RULE_LIB_PATH = os.path.join(_CSRC, "libdialupdate.so")
+
+
+def build_update_rule(force: bool = False, verbose: bool = False) -> str:
+    """libdialupdate.so: the K4a kernel of the elite update rule (csrc/update_rule.h: elite_weights_kernel; one unit, update_rule.hip,
+    the product flags) and its launcher, a library of its own so that the code objects of libdialhip.so stay as shipped.  libdialhip.so
+    loads it from its own directory the first time the elite rule is bound (dial_set_update_rule); without it that call fails."""
+    return _build_lib(UPDATE_RULE_LIB_PATH, [(os.path.join(_CSRC, "update_rule.hip"), [], "update_rule.o")], force, verbose, False)
 
 
 PLAN_ENS_LIB_PATH = os.path.join(_CSRC, "libdialplanens.so")
@@ -303,6 +316,12 @@ def load(path: Optional[str] = None):
     except AttributeError:
         if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack plan ensembles)
             raise
+    try:
+        lib.dial_set_update_rule.argtypes = [vp, ci, ci]
+        lib.dial_get_weights.argtypes = [vp, fp, ci, vp]
+    except AttributeError:
+        if path is None and "DIAL_HIP_LIB" not in os.environ:   # (A/B builds of earlier commits lack the update rules)
+            raise
     lib.dial_env_reset.argtypes = [vp, fp, fp, fp, fp, fp, vp]
     lib.dial_env_reset_batch.argtypes = [vp, fp, fp, fp, fp, fp, ci, vp]
     lib.dial_status.argtypes = [vp]
@@ -331,7 +350,8 @@ EXPORTED = ("dial_create", "dial_create_sharded", "dial_create_ex", "dial_set_st
             "dial_reverse_once_batch", "dial_reverse_once_batch_rng", "dial_shift_batch", "dial_env_step_batch",
             "dial_create_plugin", "dial_set_user_params", "dial_set_plan_params", "dial_plant_step", "dial_user_control",
             "dial_set_user_table", "dial_set_plant_disturbance", "dial_set_plant_models",
-            "dial_set_plan_models", "dial_set_plan_ensemble", "dial_get_ensemble_rewards")
+            "dial_set_plan_models", "dial_set_plan_ensemble", "dial_get_ensemble_rewards",
+            "dial_set_update_rule", "dial_get_weights")
 
 # dial_plant_step flags (include/dial_mpc.h)
 PLANT_CTRL, PLANT_PD, PLANT_HOLD_FIRST = (_abi.MACROS[k] for k in ("DIAL_PLANT_CTRL", "DIAL_PLANT_PD", "DIAL_PLANT_HOLD_FIRST"))
@@ -428,6 +448,36 @@ def plan_ensemble_index(hyp, V: int, rows: int, R: Optional[int] = None) -> np.n
     if not 1 <= a.shape[1] <= MAX_ENSEMBLE:
         raise ValueError(f"plan ensemble: R = {a.shape[1]} hypotheses per plan; 1 .. DIAL_MAX_ENSEMBLE = {MAX_ENSEMBLE} are allowed")
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+# update rules (dial_set_update_rule): how a plan's rewards become the weights of its candidates
+UPDATE_RULES = {"mppi": _abi.MACROS["DIAL_UPDATE_MPPI"], "elite": _abi.MACROS["DIAL_UPDATE_ELITE"]}
+UPDATE_METHODS = {"mppi": "mppi", "cem": "elite", "ps": "elite"}   # DialConfig.update_method -> the rule that serves it
+
+
+def elite_count(method: str, Nsample: int, elite_frac: float = 0.1, n_elite: int = 0) -> int:
+    """The elite count K of DialConfig.update_method `method` over Nsample noisy samples and the mean trajectory: "ps" (best sample)
+    -> 1; "cem" (elite mean) -> n_elite when it is above 0, else ceil(round(elite_frac * Nsample, 9)), at least 1 (the rounding keeps
+    0.1 * 2000-style products that land one ulp above an integer from gaining an elite).  Raises KeyError for another method ("mppi"
+    has no elite count), ValueError for elite_frac outside (0, 1], a negative n_elite or a count above Nsample + 1."""
+    import math
+    if method == "ps":
+        return 1
+    if method != "cem":
+        raise KeyError(method)
+    Nsample, n_elite = int(Nsample), int(n_elite)
+    if n_elite < 0:
+        raise ValueError(f"elite count: n_elite = {n_elite} is negative (0: derive it from elite_frac)")
+    if n_elite > 0:
+        K = n_elite
+    else:
+        frac = float(elite_frac)
+        if not 0.0 < frac <= 1.0:   # (a NaN fails both comparisons)
+            raise ValueError(f"elite count: elite_frac = {elite_frac!r} is outside (0, 1]")
+        K = max(1, math.ceil(round(frac * Nsample, 9)))
+    if K > Nsample + 1:
+        raise ValueError(f"elite count: K = {K} exceeds the Nsample + 1 = {Nsample + 1} candidates of a plan")
+    return K
 
 
 def plan_param_rows(rows) -> np.ndarray:
@@ -796,6 +846,24 @@ class Context:
         R = getattr(self, "_ens_R", 0)
         out = torch.empty((max(R, 1), int(M), self.cfg.Nsample + 1), dtype=torch.float32, device=self.torch_device)
         self._check(self.lib.dial_get_ensemble_rewards(self.h, _ptr(out), int(M), _stream()), "dial_get_ensemble_rewards")
+        return out
+
+    def set_update_rule(self, rule, n_elite: int = 0):
+        """The rule that turns a plan's rewards into weights (dial_set_update_rule): "mppi" (the softmax, the default) or "elite" with
+        the elite count n_elite in 1 .. Nsample + 1 -- uniform weights on the n_elite best candidates (ties by ascending index, NaN
+        last), zero on the rest; the DIAL_UPDATE_* values are taken too.  No synchronisation: launches issued afterwards use it."""
+        if isinstance(rule, str):
+            if rule not in UPDATE_RULES:
+                raise ValueError(f"update rule {rule!r}; one of {sorted(UPDATE_RULES)}")
+            rule = UPDATE_RULES[rule]
+        self._check(self.lib.dial_set_update_rule(self.h, int(rule), int(n_elite)), "dial_set_update_rule")
+
+    def weights(self, M: int = 1):
+        """The weights the last iteration formed (dial_get_weights; the softmax weights under "mppi" too): [M, Nsample + 1], M the
+        plans of that launch.  On a sharded context M = 1 and the first n_total + 1 entries are that launch's."""
+        import torch
+        out = torch.zeros((int(M), self.cfg.Nsample + 1), dtype=torch.float32, device=self.torch_device)
+        self._check(self.lib.dial_get_weights(self.h, _ptr(out), int(M), _stream()), "dial_get_weights")
         return out
 
     # ---- K3

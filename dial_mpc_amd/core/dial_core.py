@@ -37,6 +37,16 @@ def softmax_update(weights, Y0s, sigma, mu_0t):
     return torch.einsum("n,nij->ij", weights, Y0s), sigma
 
 
+def elite_update(weights, Y0s, sigma, mu_0t):
+    """The update of "cem" / "ps" (kept for API parity, like softmax_update): the same einsum over the elite weights -- 1 / K on the K
+    best candidates, zero elsewhere (include/dial_mpc.h: DIAL_UPDATE_ELITE).  sigma passes through: the noise schedule stays DIAL's."""
+    import torch
+    return torch.einsum("n,nij->ij", weights, Y0s), sigma
+
+
+UPDATE_FNS = {"mppi": softmax_update, "cem": elite_update, "ps": elite_update}
+
+
 class MBDPI:
     def __init__(self, args: DialConfig, env, device: Optional[int] = None, kernel_rng: bool = False,
                  force_sharded: bool = False, options: Optional[dict] = None, n_plans: int = 1,
@@ -53,12 +63,15 @@ class MBDPI:
         import torch
         self.kernel_rng = bool(kernel_rng)
         self._rng_counter = 0
-        self._plan = None    # preallocated buffers of the sharded iteration (core/sharding.py)
+        self._last_plans, self._last_batched = 1, False   # shape of the last call's weights (weights())
+        self._plan = None   # preallocated buffers of the sharded iteration (core/sharding.py)
         self._force_sharded = bool(force_sharded)
         self.args = args
         self.env = env
         self.nu = env.action_size
-        self.update_fn = {"mppi": softmax_update}[args.update_method]  # KeyError for anything else, as upstream
+        self.update_fn = UPDATE_FNS[args.update_method]  # KeyError for anything else, as upstream
+        if args.update_method != "mppi":   # (refuse a bad elite set before anything is created)
+            _lib.elite_count(args.update_method, args.Nsample, getattr(args, "elite_frac", 0.1), getattr(args, "n_elite", 0))
 
         sigma_control = args.horizon_diffuse_factor ** np.arange(args.Hnode + 1)[::-1]  # dial_core.py:66-70
         sigma_control = sigma_control * args.sigma_scale
@@ -103,6 +116,9 @@ class MBDPI:
         self.step_nodes = torch.as_tensor(self.step_nodes_np, dtype=torch.float32, device=dev)
         self.W = torch.as_tensor(spline.node2u_matrix(args.Hsample, args.Hnode), dtype=torch.float32, device=dev)
         self.V = torch.as_tensor(spline.u2node_matrix(args.Hsample, args.Hnode), dtype=torch.float32, device=dev)
+        self.update_method, self.n_elite = "mppi", 0
+        if args.update_method != "mppi":   # (on every rank of a sharded run: each forms the global weights itself)
+            self.set_update(args.update_method)
         self.model_of = None
         if models is not None:
             self.set_models(models, model_of, model_per)
@@ -112,6 +128,27 @@ class MBDPI:
             if unknown or "models" not in ensemble:
                 raise ValueError(f"MBDPI: ensemble is dict(models=, hyp=, aggregate=, alpha=); got keys {sorted(ensemble)}")
             self.set_ensemble(**ensemble)
+
+    # ---- update rules (dial_set_update_rule; csrc/update_rule.h)
+    def set_update(self, method: str, elite_frac: Optional[float] = None, n_elite: Optional[int] = None):
+        """Rebind the rule that turns rewards into weights; the calls issued afterwards use it.  method: "mppi" (softmax), "cem"
+        (uniform weights on the K best candidates, K = n_elite or ceil(elite_frac Nsample)) or "ps" (K = 1: the plan becomes the best
+        candidate); KeyError for anything else.  elite_frac / n_elite None: the config's.  self.args is left as it is; self.update_method
+        and self.n_elite name what is bound.  The sampling noise is not adapted from the elites.  In a sharded run every rank makes the
+        same call.  Returns K (0 for mppi)."""
+        fn = UPDATE_FNS[method]
+        frac = getattr(self.args, "elite_frac", 0.1) if elite_frac is None else elite_frac
+        ne = getattr(self.args, "n_elite", 0) if n_elite is None else n_elite
+        K = 0 if method == "mppi" else _lib.elite_count(method, self.args.Nsample, frac, ne)
+        self.ctx.set_update_rule("mppi" if K == 0 else "elite", K)
+        self.update_fn, self.update_method, self.n_elite = fn, method, K
+        return K
+
+    def weights(self):
+        """The weights the last reverse_once [N + 1] or reverse_once_batch [M, N + 1] formed (the softmax weights under mppi too), e.g.
+        for an effective sample size 1 / sum(w^2).  A sharded run returns the global weights, the same on every rank."""
+        w = self.ctx.weights(self._last_plans)
+        return w if self._last_batched else w[0]
 
     # ---- robust planning over a model ensemble (dial_set_plan_ensemble; csrc/plan_ens_kernel.h)
     def set_ensemble(self, models, hyp=None, aggregate: str = "mean", alpha: float = 1.0):
@@ -206,6 +243,7 @@ class MBDPI:
         them (dial_core.py:262-264, dial_plan.py:214-215)."""
         import torch
         packed = _packed(state)
+        self._last_plans, self._last_batched = 1, False
         if eps is None and self.kernel_rng:
             Yb = torch.as_tensor(Ybar_i, dtype=torch.float32, device=self.device).contiguous()
             nsc = torch.as_tensor(noise_scale, dtype=torch.float32, device=self.device).reshape(-1).contiguous()
@@ -267,6 +305,7 @@ class MBDPI:
             states = torch.stack([_packed(st) for st in states])
         states = torch.as_tensor(states, dtype=torch.float32, device=self.device).contiguous()
         M = int(states.shape[0])
+        self._last_plans, self._last_batched = M, True
         Ybars = torch.as_tensor(Ybars, dtype=torch.float32, device=self.device).contiguous()
         nsc = torch.as_tensor(noise_scales, dtype=torch.float32, device=self.device)
         if nsc.dim() < 2:
@@ -475,6 +514,10 @@ def main(argv=None):
                         help="M closed loops from env.reset, planned together in one launch per iteration (default 1)")
     parser.add_argument("--env-param", action="append", default=[], metavar="NAME=V1,...,VM",
                         help="custom environments with --n-envs M: closed loop g runs with task parameter NAME = Vg (repeatable)")
+    parser.add_argument("--update-method", choices=sorted(UPDATE_FNS), default=None,
+                        help="override update_method from the YAML: mppi (softmax), cem (elite mean) or ps (best sample)")
+    parser.add_argument("--elite-frac", type=float, default=None,
+                        help="override elite_frac from the YAML: cem's elites as a share of Nsample, in (0, 1] (clears n_elite)")
     args = parser.parse_args(argv)
 
     if args.list_examples:
@@ -492,6 +535,10 @@ def main(argv=None):
     dial_config, env_config, env = load_dial_and_env(config_dict)
     if args.n_steps is not None:
         dial_config.n_steps = args.n_steps
+    if args.update_method is not None:
+        dial_config.update_method = args.update_method
+    if args.elite_frac is not None:
+        dial_config.elite_frac, dial_config.n_elite = args.elite_frac, 0
     env_params = _env_params(parser, args, env)
     model_kw = _plan_models_kw(config_dict, dial_config, env, args.n_envs)
     if args.n_envs > 1:

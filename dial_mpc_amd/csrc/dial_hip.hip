@@ -9,6 +9,8 @@
 //                    at N = 8 x CUs); every wavefront re-draws its issue priority (wave.h: redraw_priority).
 //   weights_kernel   K4a: rew_bar, std, softmax over all N+1 mean rewards (one workgroup per plan, fixed
 //                    reduction order => bit-identical on every GPU of a sharded run).
+//   elite_weights_kernel  K4a under DIAL_UPDATE_ELITE (update_rule.h, in libdialupdate.so): uniform weights on the K best;
+//                    launch_weights() picks.
 //   wsum_*_kernel    K4b: weighted means of Y0s / q / qd / x.pos, two deterministic passes (plan on grid.z).
 //   shift_kernel     K5, env_step_kernel / env_reset_kernel  K6 (one workgroup per state / plan).
 // There is no CPU fallback: every entry point needs a HIP device and fails with DIAL_ERR_HIP otherwise.
@@ -30,6 +32,7 @@
 #include "plan_ens_kernel.h"
 #include "plugin_ops.h"
 #include "reward_defer_kernel.h"
+#include "update_rule.h"
 
 // the kernels are compiled in their own translation units, one per robot family (kern_family.hip, built in parallel)
 #define DIAL_X(D, WPB, OCC, Q, TR) \
@@ -393,6 +396,9 @@ struct dial_ctx {
   int plan_cap = 1;            // plans of one grouped launch (dial_options.plan_cap): the rollout scratch holds plan_cap x B_cap rollouts
   float *Y0s = nullptr, *rewss = nullptr, *rews = nullptr, *qss = nullptr, *qdss = nullptr, *xss = nullptr;
   float *weights = nullptr, *partial = nullptr;
+  int update_rule = DIAL_UPDATE_MPPI, n_elite = 0;   // the rule that forms the weights (dial_set_update_rule) and its elite count
+  dial_update_rule_launch_fn elite_launch = nullptr; // libdialupdate.so's launcher, looked up when the elite rule is first bound
+  int weights_M = 0, weights_B = 0;                  // plans x entries of ctx->weights the last K4a launch wrote (dial_get_weights), 0: none yet
   // Set while the last rollout launch left rows of the scratch above unwritten (a lean launch: DIAL_SHARD_LEAN, or a
   // reverse_once[_batch] without bars), naming it; dial_shard_reduce* would sum stale rows and refuse to run.  A full launch clears it.
   const char* rows_stale = nullptr;
@@ -478,6 +484,31 @@ static const dial_reward_defer_ops* reward_defer_ops() {
     return o;
   }();
   return ops;
+}
+
+// libdialupdate.so (update_rule.hip): the elite update rule's K4a kernel behind one launcher, looked up in this library's own
+// directory the first time the rule is bound; the IEEE measurement variant links the unit itself.  nullptr: no such file, or one
+// without the symbol -- dial_set_update_rule(DIAL_UPDATE_ELITE) then fails with DIAL_ERR_UNSUPPORTED (there is no other elite path).
+#ifdef DIAL_IEEE_BUILD
+extern "C" hipError_t dial_update_rule_launch_v1(hipStream_t, int, const float*, int, int, float*, const float*, int, float*);
+static dial_update_rule_launch_fn update_rule_load() { return &dial_update_rule_launch_v1; }
+#else
+static dial_update_rule_launch_fn update_rule_load() {
+  std::string dir = ".";
+  Dl_info info;
+  if (dladdr((const void*)&update_rule_load, &info) && info.dli_fname) {
+    dir = info.dli_fname;
+    const size_t slash = dir.rfind('/');
+    dir = slash == std::string::npos ? "." : dir.substr(0, slash);
+  }
+  const std::string path = dir + "/libdialupdate.so";
+  void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);   // (never dlclose'd: the runtime holds its code objects)
+  return h ? (dial_update_rule_launch_fn)dlsym(h, DIAL_UPDATE_RULE_SYMBOL) : nullptr;
+}
+#endif
+static dial_update_rule_launch_fn update_rule_launcher() {
+  static const dial_update_rule_launch_fn fn = update_rule_load();   // (once per process, thread-safe initialisation)
+  return fn;
 }
 
 static int fail(dial_ctx* ctx, int code, const std::string& msg) {
@@ -1523,6 +1554,26 @@ static int launch_wsum(dial_ctx* ctx, const float* weights, int n_rows, int w_be
   return DIAL_OK;
 }
 
+// K4a of every launch path: the weights of `plans` plans from rews [plans][B] -> ctx->weights, by the context's update rule
+// (dial_set_update_rule).  DIAL_UPDATE_MPPI is weights_kernel with the arguments it always had.  gathered / per / rews_out: the packing
+// first pass of the sharded phase B (one plan).  On the sharded entry points B = n_total + 1 may be smaller than the Nsample + 1 the
+// elite count was checked against: K > B fails here.
+static int launch_weights(dial_ctx* ctx, hipStream_t st, int plans, const float* rews, int B, const float* gathered, int per, float* rews_out) {
+  static_assert(UR_THREADS == WK_THREADS, "the two K4a kernels share their launch shape");
+  if (ctx->update_rule == DIAL_UPDATE_ELITE) {
+    if (ctx->n_elite > B)
+      return fail(ctx, DIAL_ERR_ARG, "dial_set_update_rule: the bound elite count " + std::to_string(ctx->n_elite) + " exceeds the " + std::to_string(B) +
+                                     " candidates of this launch (n_total + 1)");
+    HIP_TRY(ctx, ctx->elite_launch(st, plans, rews, B, ctx->n_elite, ctx->weights, gathered, per, rews_out));   // (libdialupdate.so)
+  } else {
+    hipLaunchKernelGGL(weights_kernel, dim3(plans), dim3(WK_THREADS), 0, st, rews, B, ctx->hc.temp_sample, ctx->weights, gathered, per, rews_out);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  ctx->weights_M = plans;
+  ctx->weights_B = B;
+  return DIAL_OK;
+}
+
 // gathered != nullptr: the rewards as the all-gather delivered them ([world][per + 1]); the weights kernel puts them in order on the
 // way (-> rews_out).  Otherwise rews_all is read as is.
 static int shard_reduce_impl(dial_ctx* ctx, const float* rews_all, const float* gathered, int world, int per, float* rews_out,
@@ -1538,8 +1589,7 @@ static int shard_reduce_impl(dial_ctx* ctx, const float* rews_all, const float* 
   hipStream_t st = (hipStream_t)stream;
   // the global weights need n_total+1 floats of ctx->weights
   if (n_total + 1 > ctx->W_cap) return fail(ctx, DIAL_ERR_ARG, std::string(who) + ": n_total exceeds the context's Nsample (create it with Nsample = global sample count)");
-  hipLaunchKernelGGL(weights_kernel, dim3(1), dim3(WK_THREADS), 0, st, rews_all, n_total + 1, ctx->hc.temp_sample, ctx->weights, gathered, per, rews_out);
-  HIP_TRY(ctx, hipGetLastError());
+  if (int rcw = launch_weights(ctx, st, 1, rews_all, n_total + 1, gathered, per, rews_out)) return rcw;
   const dial_model& m = ctx->hm;
   float* Yo = packed_out;
   float* qo = Yo + ctx->Hn1 * m.nu;
@@ -1575,8 +1625,7 @@ static int shard_ybar_impl(dial_ctx* ctx, const float* rews_all, const float* ga
   hipStream_t st = (hipStream_t)stream;
   const int C = ctx->Hn1 * ctx->hm.nu, nquad = (C + 3) / 4;
   static_assert(YB_CHUNKS == YB_CHUNKS_HOST, "the scratch buffer is sized with YB_CHUNKS_HOST");
-  hipLaunchKernelGGL(weights_kernel, dim3(1), dim3(WK_THREADS), 0, st, rews_all, n_total + 1, ctx->hc.temp_sample, ctx->weights, gathered, per, rews_out);
-  HIP_TRY(ctx, hipGetLastError());
+  if (int rcw = launch_weights(ctx, st, 1, rews_all, n_total + 1, gathered, per, rews_out)) return rcw;
   hipLaunchKernelGGL(ybar_partial_kernel, dim3((nquad + 15) / 16, YB_CHUNKS), dim3(256), 0, st, (const float*)ctx->weights,
                      eps_all, Ybar_in, noise_scale, ns, n_total, C, ctx->hm.nu, ctx->partial,
                      (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), counter);
@@ -1642,8 +1691,7 @@ static int reverse_once_ens(dial_ctx* ctx, const float* states, const float* Yba
   if (int rc = launch_rollout(ctx, io, M * (N + 1), st, M)) return rc;
   if (bars) ctx->rows_stale = nullptr;
   HIP_TRY(ctx, ctx->ens_aggregate(st, ctx->ens_raw, rews, ctx->ens_R, M * (N + 1), ctx->ens_mode, ctx->ens_k));
-  hipLaunchKernelGGL(weights_kernel, dim3(M), dim3(WK_THREADS), 0, st, (const float*)rews, N + 1, ctx->hc.temp_sample, ctx->weights, (const float*)nullptr, 0, (float*)nullptr);
-  HIP_TRY(ctx, hipGetLastError());
+  if (int rcw = launch_weights(ctx, st, M, (const float*)rews, N + 1, (const float*)nullptr, 0, (float*)nullptr)) return rcw;
   return launch_wsum(ctx, ctx->weights, N + 1, 0, N, N, Ybar_out, qbar, qdbar, xbar, st, !bars, M);
 }
 
@@ -1665,8 +1713,7 @@ static int reverse_once_impl(dial_ctx* ctx, const float* state, const float* Yba
   int rc = shard_rollout_impl(ctx, state, Ybar_in, noise_scale, ns, eps, use_rng, seed, counter, 0, N, 1, rews, stream, who, bars);
   if (rc != DIAL_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(weights_kernel, dim3(1), dim3(WK_THREADS), 0, st, (const float*)rews, N + 1, ctx->hc.temp_sample, ctx->weights, (const float*)nullptr, 0, (float*)nullptr);
-  HIP_TRY(ctx, hipGetLastError());
+  if (int rcw = launch_weights(ctx, st, 1, (const float*)rews, N + 1, (const float*)nullptr, 0, (float*)nullptr)) return rcw;
   return launch_wsum(ctx, ctx->weights, N + 1, 0, N, N, Ybar_out, qbar, qdbar, xbar, st, !bars);
 }
 
@@ -1714,8 +1761,7 @@ static int reverse_once_batch_impl(dial_ctx* ctx, const float* states, const flo
   if (!bars) ctx->rows_stale = "the last rollout launch formed the mean action only (reverse_once_batch without bars): it wrote no per-step states";
   if (int rc = launch_rollout(ctx, io, B, st)) return rc;
   if (bars) ctx->rows_stale = nullptr;
-  hipLaunchKernelGGL(weights_kernel, dim3(M), dim3(WK_THREADS), 0, st, (const float*)rews, N + 1, ctx->hc.temp_sample, ctx->weights, (const float*)nullptr, 0, (float*)nullptr);
-  HIP_TRY(ctx, hipGetLastError());
+  if (int rcw = launch_weights(ctx, st, M, (const float*)rews, N + 1, (const float*)nullptr, 0, (float*)nullptr)) return rcw;
   return launch_wsum(ctx, ctx->weights, N + 1, 0, N, N, Ybar_out, qbar, qdbar, xbar, st, !bars, M);
 }
 
@@ -2411,6 +2457,37 @@ int dial_get_ensemble_rewards(dial_ctx* ctx, float* out, int M, void* stream) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipMemcpyAsync(out, ctx->ens_raw, (size_t)ctx->ens_R * M * (ctx->hc.Nsample + 1) * sizeof(float), hipMemcpyDeviceToDevice,
                               (hipStream_t)stream));
+  return DIAL_OK;
+}
+
+int dial_set_update_rule(dial_ctx* ctx, int rule, int n_elite) {
+  if (!ctx) return fail(nullptr, DIAL_ERR_ARG, "dial_set_update_rule: null context");
+  if (!ctx->has_cfg) return fail(ctx, DIAL_ERR_ARG, "dial_set_update_rule: context was created without a dial_cfg (it forms no weights)");
+  if (rule != DIAL_UPDATE_MPPI && rule != DIAL_UPDATE_ELITE)
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_update_rule: unknown rule " + std::to_string(rule) + " (DIAL_UPDATE_MPPI = 0, DIAL_UPDATE_ELITE = 1)");
+  if (rule == DIAL_UPDATE_ELITE && (n_elite < 1 || n_elite > ctx->hc.Nsample + 1))
+    return fail(ctx, DIAL_ERR_ARG, "dial_set_update_rule: n_elite = " + std::to_string(n_elite) + " is outside 1 .. Nsample + 1 = " +
+                                   std::to_string(ctx->hc.Nsample + 1));
+  if (rule == DIAL_UPDATE_ELITE && !ctx->elite_launch) {
+    ctx->elite_launch = update_rule_launcher();
+    if (!ctx->elite_launch)
+      return fail(ctx, DIAL_ERR_UNSUPPORTED, "dial_set_update_rule: libdialupdate.so (the elite rule's kernel) is missing next to this library or "
+                                             "lacks " DIAL_UPDATE_RULE_SYMBOL ": run the build");
+  }
+  ctx->update_rule = rule;
+  ctx->n_elite = rule == DIAL_UPDATE_ELITE ? n_elite : 0;
+  return DIAL_OK;
+}
+
+int dial_get_weights(dial_ctx* ctx, float* out, int M, void* stream) {
+  if (!ctx) return fail(nullptr, DIAL_ERR_ARG, "dial_get_weights: null context");
+  if (!out) return fail(ctx, DIAL_ERR_ARG, "dial_get_weights: null argument");
+  if (ctx->weights_M == 0) return fail(ctx, DIAL_ERR_ARG, "dial_get_weights: no iteration has formed weights on this context yet");
+  if (M != ctx->weights_M)
+    return fail(ctx, DIAL_ERR_ARG, "dial_get_weights: M = " + std::to_string(M) + ", the last launch formed the weights of " +
+                                   std::to_string(ctx->weights_M) + " plans");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->weights, (size_t)M * ctx->weights_B * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return DIAL_OK;
 }
 

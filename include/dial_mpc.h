@@ -761,6 +761,33 @@ int dial_set_plan_ensemble(dial_ctx* ctx, const dial_model* models, int V, const
  * or when M differs from that launch's M. */
 int dial_get_ensemble_rewards(dial_ctx* ctx, float* out /* device, [R][M][Nsample+1] */, int M, void* stream);
 
+/* Update rules: how the B rewards of a plan become the weights of its candidates.  B = Nsample + 1 with the mean trajectory last
+ * (n_total + 1 on the sharded entry points).  The rule lives in the context; every launch path reads it -- dial_reverse_once[_rng],
+ * dial_reverse_once_batch[_rng] (each plan on its own row), the robust iteration of a bound ensemble (on the aggregated rewards),
+ * task-plugin contexts, and the sharded dial_shard_reduce* / dial_shard_ybar*.  Everything after the weights is unchanged: Ybar,
+ * qbar, qdbar and xbar are the same weighted sums.
+ *   DIAL_UPDATE_MPPI (the default): the softmax of (rews - rew_bar) / std(rews) / temp_sample, exactly the launch of a context that
+ *     never called dial_set_update_rule.  std(rews) == 0 gives NaN weights, as the reference does.
+ *   DIAL_UPDATE_ELITE with an elite count K, 1 <= K <= B: order the B candidates by reward, best first -- a NaN ranks below every
+ *     number, -inf included; -0 equals +0; equal rewards are ordered by ascending index.  The first K candidates in this order are
+ *     the elites: each gets weights[n] = 1.0f / (float)K (one correctly rounded fp32 division: the same bit pattern in every elite,
+ *     exactly 1.0f for K = 1), every other candidate +0.0f.  temp_sample is not read; identical rewards give no NaN (the first K
+ *     indices win).  K = ceil(elite_frac Nsample) is the elite mean of the cross-entropy method, K = 1 the best sample (predictive
+ *     sampling: the plan becomes the best candidate, the current mean trajectory among them).
+ * The sampling noise is NOT adapted from the elites: noise_scale stays the caller's input (DIAL's annealing schedule).
+ * dial_set_update_rule: no synchronisation, launches issued afterwards use the new rule; n_elite is ignored for DIAL_UPDATE_MPPI.
+ * Fails with DIAL_ERR_ARG and a message that starts with "dial_set_update_rule: " on a null context, an unknown rule, n_elite
+ * outside 1 .. Nsample + 1, or a context created without a dial_cfg.  A sharded call whose n_total + 1 is below the bound K fails
+ * with DIAL_ERR_ARG (same prefix) when it would form the weights. */
+#define DIAL_UPDATE_MPPI  0
+#define DIAL_UPDATE_ELITE 1
+int dial_set_update_rule(dial_ctx* ctx, int rule, int n_elite);
+/* The weights the context's last iteration formed (the softmax weights under DIAL_UPDATE_MPPI too): an asynchronous device-to-device
+ * copy on `stream` into out:[M][Nsample + 1], M the number of plans of that launch (1 for every entry point but
+ * dial_reverse_once_batch*; on a sharded context M = 1 and n_total + 1 entries are written).  Fails with DIAL_ERR_ARG before the first
+ * launch that forms weights and when M differs from that launch's. */
+int dial_get_weights(dial_ctx* ctx, float* out /* device, [M][Nsample+1] */, int M, void* stream);
+
 /* ABI self-description used by tests: sizeof of the three structs. */
 int dial_abi_sizes(int* model_bytes, int* task_bytes, int* cfg_bytes);
 
