@@ -832,6 +832,13 @@ static int create_impl(dial_ctx** out, const dial_model* model, const dial_task*
   // (checked below)
   if (model->cone == DIAL_CONE_PYRAMIDAL && model->eulerdamp)
     return fail(nullptr, DIAL_ERR_UNSUPPORTED, "dial_create: eulerdamp is only supported on the elliptic-cone instantiations");
+  // sphere-capsule and capsule-capsule narrow phases exist in the elliptic instantiations and in task plugins (rollout_body.h:
+  // collide_contact); the built-in pyramidal kernels would read such a slot as a plane contact
+  if (model->cone == DIAL_CONE_PYRAMIDAL && !plug)
+    for (int c = 0; c < model->ncon; c++)
+      if (model->con_kind[c] == DIAL_CON_SPHERE_CAPSULE || model->con_kind[c] == DIAL_CON_CAPSULE_CAPSULE)
+        return fail(nullptr, DIAL_ERR_UNSUPPORTED, "dial_create: sphere-capsule and capsule-capsule contacts of a pyramidal model run on a task "
+                                                   "plugin only (dial_create_plugin); exclude the pair or build a plugin for the model");
   if (model->nefc > DIAL_MAX_EFC || model->nv > DIAL_MAX_V ||
       model->nq + 2 * model->nv + DIAL_INFO_N > 4096)
     return fail(nullptr, DIAL_ERR_ARG, "dial_create: model exceeds kernel capacities");
@@ -843,7 +850,11 @@ static int create_impl(dial_ctx** out, const dial_model* model, const dial_task*
   ctx->ht = *task;
   ctx->plug = plug;
   int rc = dial_build_derived(model, &ctx->hd);
-  if (rc != DIAL_OK) { delete ctx; return fail(nullptr, rc, "dial_create: unsupported model topology"); }
+  if (rc != DIAL_OK) {
+    delete ctx;
+    return fail(nullptr, rc, "dial_create: unsupported model topology (a root-to-body path of more than 12 dofs, two actuators on one "
+                             "dof, or more than 32 dofs)");
+  }
   ctx->nx = (model->nbody - 1) * 3;
   // from here on every failure path releases the half-built context (dial_destroy frees whatever was allocated)
 #define HIP_TRY_CREATE(expr)                                                                          \

@@ -993,7 +993,7 @@ DIAL_DEV void shared_subtree_sum(const M* m, int k, int st, const float* own, fl
   }
 }
 
-// collision_driver: contact c of the static list (narrow phases: plane-sphere / plane-capsule end; elliptic models also
+// collision_driver: contact c of the static list (narrow phases: plane-sphere / plane-capsule end; elliptic models and task plugins also
 // sphere-capsule and capsule-capsule; generic feature set also the box routines of box_collide.h)
 template <class M>
 DIAL_DEV void collide_contact(const M* m, const Ws& s, int c) {
@@ -1031,7 +1031,9 @@ DIAL_DEV void collide_contact(const M* m, const Ws& s, int c) {
       return;
     }
   }
-  if constexpr (M::D::ell) {
+  // (pyramidal models: a task plugin's instantiation only -- the branch vanishes from every built-in instantiation, whose models
+  // have no such pair; dial_create refuses a pyramidal model with one on the capacity-dimension kernel)
+  if constexpr (M::D::ell || M::D::user) {
     if (m->con_kind[c] == DIAL_CON_SPHERE_CAPSULE || m->con_kind[c] == DIAL_CON_CAPSULE_CAPSULE) {
       // MJX sphere_capsule / capsule_capsule: closest points on the capsule segment(s), then _sphere_sphere
       const float ax2[3] = {s.gaxis[3 * g2], s.gaxis[3 * g2 + 1], s.gaxis[3 * g2 + 2]}, hl2 = m->geom_size[g2][1];
@@ -1055,7 +1057,7 @@ DIAL_DEV void collide_contact(const M* m, const Ws& s, int c) {
       s.cdist[c] = dist;
       for (int k = 0; k < 3; k++) s.cpos[3 * c + k] = p1[k] + nn[k] * (r1 + dist * 0.5f);
       make_frame(fr, nn);
-      s.con_on[c] = (dist - m->con_margin[c]) < 0.f ? 1.f : 0.f;
+      if constexpr (M::D::ell) s.con_on[c] = (dist - m->con_margin[c]) < 0.f ? 1.f : 0.f;
       return;
     }
   }

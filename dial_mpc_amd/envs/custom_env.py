@@ -14,7 +14,10 @@ A subclass sets
                    counter -- ``table_row(step, table_row0, rows, table_mode)``.  ``table_mode`` "clamp" (default) or "wrap",
 and registers itself with ``dial_mpc_amd.envs.register_environment`` / ``register_config``.  Without ``control_hip`` control is
 BaseEnv's (act2joint / act2tau with the config's leg_control, kp, kd, action_scale); the sampling range is the joint range of the
-model unless the subclass sets ``self.joint_range``.  Under ``leg_control: torque`` the PD law reads actuator a's joint as
+model unless the subclass sets ``self.joint_range``: actuator a's row is the range of the joint IT drives (``actuator_joint_range``;
+BaseEnv's ``jnt_range[1:]`` where the first joint is a free base and the actuators follow the joints in order).  A model no task plugin
+can serve (implicit damping, elliptic cones, a dof path of more than 12, two actuators on a dof) is refused in ``__init__``
+(``plugin.check_model``).  Under ``leg_control: torque`` the PD law reads actuator a's joint as
 qpos[7 + a] / qvel[6 + a] (BaseEnv.act2tau): the model must have a free base joint and actuators that drive dofs 6, 7, ... in
 order; a model that does not is refused (``torque_joint_convention``).
 
@@ -53,6 +56,13 @@ def torque_joint_convention(model: Dict[str, Any]) -> None:
                          f"indexing of BaseEnv.act2tau); {what}.  Reorder the model's actuators or use leg_control: position")
 
 
+def actuator_joint_range(model: Dict[str, Any]) -> np.ndarray:
+    """[nu, 2]: the range of the joint each actuator drives (slide / hinge joints: the joint whose qpos address is act_qposadr)."""
+    qadr = np.asarray(model["jnt_qposadr"]).ravel().tolist()
+    rng = np.asarray(model["jnt_range"], dtype=np.float64).reshape(-1, 2)
+    return np.array([rng[qadr.index(int(a))] for a in np.asarray(model["act_qposadr"]).ravel()[:int(model["nu"])]]).reshape(-1, 2)
+
+
 def table_row(step: int, row0: int, rows: int, mode="clamp") -> int:
     """The reference-table row of the control step whose step counter is `step` (the counter BEFORE the step): the host restatement
     of the kernels' rule (csrc/user_reward.h).  r = step + row0; "clamp": min(max(r, 0), rows - 1); "wrap": r modulo rows."""
@@ -79,8 +89,14 @@ class CustomEnv(BaseEnv):
         if not self.model_path or not self.reward_hip:
             raise TypeError(f"{type(self).__name__}: a CustomEnv subclass sets model_path and reward_hip")
         super().__init__(config)
+        from dial_mpc_amd.plugin import check_model
+        check_model(self.sys.model)   # what no plugin can serve (implicit damping, elliptic cones, tree shapes) is refused here
         if config.leg_control == "torque" and not self.control_hip:   # (a control law indexes its own joints)
             torque_joint_convention(self.sys.model)
+        # BaseEnv takes the joints after the first one, a free base joint, as the actuated ones.  A model whose first joint is
+        # not free, or whose actuators skip joints: actuator a's ranges are those of ITS joint (the same rows where BaseEnv's fit)
+        self.physical_joint_range = actuator_joint_range(self.sys.model)
+        self.joint_range = self.physical_joint_range
         self._init_q = np.asarray(self.sys.model["keyframes"][self.init_keyframe], dtype=np.float64)
         self._plugin = None
 

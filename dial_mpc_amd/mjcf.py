@@ -6,7 +6,7 @@ not a dependency here, so this module implements the subset of the MJCF compiler
 needs: ``<include>``, nested ``<default>`` classes / ``childclass``,
 ``<compiler angle autolimits>``, ``<option>`` + ``<flag>``, bodies / inertials / joints (free,
 hinge, slide) / geoms (plane, sphere, capsule incl. ``fromto``) / sites / actuators (motor,
-position) / keyframes / ``<contact><exclude>``, the static contact list (plane-sphere, plane-capsule,
+position) / keyframes / ``<contact><exclude>`` (``<contact><pair>`` raises NotImplementedError), the static contact list (plane-sphere, plane-capsule,
 sphere-capsule, capsule-capsule) with MuJoCo's parameter mixing rules (priority, condim, solmix,
 friction), pyramidal and elliptic cones, and the quantities MuJoCo derives at ``qpos0``: ``body_invweight0``,
 ``dof_invweight0`` and ``stat.meaninertia``.
@@ -500,6 +500,11 @@ def compile_mjcf(path: str, mesh_inertia: str = "convex") -> Dict[str, Any]:
     excludes = set()
     names_b = [b["name"] for b in bodies]
     for c in root.findall("contact"):
+        if c.find("pair") is not None:
+            # (an explicit pair carries its own condim / friction / solref / margin and bypasses the contype / conaffinity filter;
+            # dropping it silently would remove a contact the user asked for)
+            raise NotImplementedError("<contact><pair> is not supported: select contacts with contype / conaffinity and "
+                                      "<contact><exclude>, and set their parameters on the geoms")
         for ex in c.findall("exclude"):
             b1, b2 = names_b.index(ex.attrib["body1"]), names_b.index(ex.attrib["body2"])
             excludes.add((min(b1, b2), max(b1, b2)))

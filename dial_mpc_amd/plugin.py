@@ -84,11 +84,42 @@ def kbi_unique_rows(model) -> int:
     return len(rows)
 
 
+def check_topology(model) -> None:
+    """Raise DialHipError for the tree shapes dial_create answers with DIAL_ERR_UNSUPPORTED (csrc/derived.h: dial_build_derived),
+    with the body or the actuators it is about: a root-to-body path of more than 12 dofs, two actuators on one dof."""
+    d = _model_dict(model)
+    nb, nu = int(d["nbody"]), int(d["nu"])
+    parent, dofnum = np.asarray(d["body_parent"]).ravel(), np.asarray(d["body_dofnum"]).ravel()
+    names = d.get("names", {}) if isinstance(d, dict) else {}
+    for b in range(1, nb):
+        n, bb = 0, b
+        while bb > 0:
+            n += int(dofnum[bb])
+            bb = int(parent[bb])
+        if n > 12:
+            who = repr(names["body"][b]) if names.get("body") else str(b)
+            raise DialHipError(f"body {who} is moved by {n} dofs between the world and itself; the kernels' ancestor lists hold 12 "
+                               "(a free joint counts 6): shorten the chain or weld a joint")
+    seen: Dict[int, int] = {}
+    for a in range(nu):
+        dof = int(np.asarray(d["act_dofadr"]).ravel()[a])
+        if dof in seen:
+            who = [repr(names["actuator"][k]) if names.get("actuator") else str(k) for k in (seen[dof], a)]
+            raise DialHipError(f"actuators {who[0]} and {who[1]} both drive dof {dof}; the kernels take one actuator per dof: merge "
+                               "them into one actuator")
+        seen[dof] = a
+
+
 def check_model(model) -> None:
     """Raise DialHipError when a task plugin cannot serve `model` (csrc/plugin_ops.h: PluginOps::check)."""
     d = _model_dict(model)
     if int(d.get("cone", 0)) != _abi.MACROS["DIAL_CONE_PYRAMIDAL"]:
         raise DialHipError("task plugins support pyramidal friction cones only: the model uses elliptic cones")
+    if int(d.get("eulerdamp", 0)):
+        raise DialHipError("the model integrates joint damping implicitly (MuJoCo's default whenever a joint has damping > 0); the "
+                           "pyramidal kernels integrate it explicitly: add <option><flag eulerdamp=\"disable\"/></option> to the MJCF "
+                           "(dial_create refuses eulerdamp on every pyramidal model)")
+    check_topology(d)
     n, cap = kbi_unique_rows(d), _kbi_rows_capacity()
     if n > cap:
         raise DialHipError(f"the model has {n} distinct (solref, solimp) sets; the impedance table of a plugin holds "

@@ -28,6 +28,19 @@ def build(defines=(), tag=""):
     return so
 
 
+def user_variant(model, reward_path):
+    """(defines, tag) of the emulator variant that also carries a TASK PLUGIN's instantiation -- DimsUser at `model`'s dimensions with
+    the reward source at `reward_path`, as csrc/plugin.hip instantiates it (emu.cpp: DIAL_EMU_USER).  Emu(model, task, cfg, path=0,
+    defines=..., tag=...) then runs a model of those dimensions on it; set_user_params sets the reward's parameters."""
+    import hashlib
+    from dial_mpc_amd.plugin import DIM_NAMES, _DIM_MACROS, plugin_dims
+    dims = plugin_dims(model)
+    defines = ["-DDIAL_EMU_USER=1", f'-DDIAL_EMU_USER_REWARD="{os.path.abspath(reward_path)}"']
+    defines += [f"-DDIAL_PLUGIN_{m}={dims[k]}" for k, m in zip(DIM_NAMES, _DIM_MACROS)]
+    key = hashlib.sha256((" ".join(defines) + open(reward_path).read()).encode()).hexdigest()[:12]
+    return tuple(defines), "_user_" + key
+
+
 class Emu:
     def __init__(self, model, task, cfg=None, path=0, defines=(), tag=""):
         """path 0: dimension-specialised instantiation when the model matches one (like the HIP library);
@@ -115,6 +128,26 @@ class Emu:
         rc = self.lib.emu_box_contact(int(kind), int(sub), self._p(a), self._p(b), self._p(dist), self._p(pos), self._p(frame))
         assert rc == 0
         return float(dist[0]), pos.astype(np.float64), frame.reshape(3, 3).astype(np.float64)
+
+    def set_user_params(self, params):
+        """The reward parameters of a user_variant build (process-wide in that library)."""
+        p = self._a(params)
+        assert self.lib.emu_set_user_params(self._p(p), int(p.size)) == 0
+
+    def derived(self):
+        """The derived tables of the model (csrc/derived.h) -> dict(rc, nlevel, lvl_start, lvl_body, body_ancmask, dof_ancmask, hitem);
+        hitem as (i, j, P, writer, n, contacts) per work-list item.  rc != 0: dial_build_derived refused the model (the rest is absent)."""
+        m = self.model
+        levels, masks = np.zeros(2 * m.nbody + 2, np.int32), np.zeros(m.nbody + m.nv, np.uint32)
+        items, nh = np.zeros(512, np.uint32), ctypes.c_int()
+        rc = self.lib.emu_derived(ctypes.byref(m), self._p(levels), self._p(masks), ctypes.byref(nh), self._p(items), 512)
+        if rc:
+            return dict(rc=rc)
+        nl = int(levels[0])
+        hitem = [(int(h & 31), int((h >> 5) & 31), (1, 2, 4)[int((h >> 10) & 3)], int((h >> 12) & 1), int((h >> 14) & 7),
+                  [int((h >> (17 + 3 * k)) & 7) for k in range(int((h >> 14) & 7))]) for h in items[:nh.value].tolist()]
+        return dict(rc=0, nlevel=nl, lvl_start=levels[1:nl + 2].tolist(), lvl_body=levels[nl + 2:nl + 1 + m.nbody].tolist(),
+                    body_ancmask=masks[:m.nbody].tolist(), dof_ancmask=masks[m.nbody:].tolist(), hitem=hitem)
 
     def sizes(self):
         """(which instantiation: 0 generic / 1 Go2 / 2 H1, sizeof(CModel), workspace words)."""

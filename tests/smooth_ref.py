@@ -165,6 +165,12 @@ def rollout_cases(example, count=4, B=16, seed=11):
     within two control steps whatever the noise)."""
     _, env, model, task, cfg = case(example)
     o64, _ = oracles(example)
+    return rollout_cases_for(example, env, model, task, cfg, o64, count, B, seed)
+
+
+def rollout_cases_for(example, env, model, task, cfg, o64, count=4, B=16, seed=11):
+    """rollout_cases for any (env, model, task, cfg) with its fp64 oracle -- a model that is no shipped example (`example` only
+    names it in messages)."""
     T = cfg.Hsample + 1
     q, v, _ = smooth_states(env, model, "F", 4 * count, seed)
     hand = model.cone == _abi.MACROS["DIAL_CONE_ELLIPTIC"]
@@ -250,7 +256,9 @@ class Gate:
         """qpos / base qvel / joint qvel blocks of [cases, nq] and [cases, nv] arrays; ref = (q, qd)."""
         base = base_dofs(model)
         self.block("qpos", step, q, ref64[0], ref32[0], qpos=True)
-        self.block("base_qvel", step, qd[..., base], ref64[1][..., base], ref32[1][..., base])
+        assert bool(base.any()) == any(int(model.jnt_type[j]) == FREE for j in range(model.njnt)), "base_dofs missed a free joint"
+        if base.any():   # (a model without a free joint has no base block)
+            self.block("base_qvel", step, qd[..., base], ref64[1][..., base], ref32[1][..., base])
         if (~base).any():
             self.block("joint_qvel", step, qd[..., ~base], ref64[1][..., ~base], ref32[1][..., ~base])
 

@@ -66,23 +66,69 @@ def _case(example, seed):
     return env, md, model, task, cfg, np.asarray(q, np.float64), np.asarray(qd, np.float64)
 
 
-@pytest.mark.parametrize("example,_n", ROBOTS)
-def test_mass_matrix_is_the_hessian_of_the_kinetic_energy(example, _n):
-    env, md, model, task, cfg, q, qd = _case(example, 3)
-    o64 = O.Oracle(model, task, cfg, np.float64)
-    M = o64.forward_dump(q, np.zeros(md["nv"]))["qM"]
+def check_mass_matrix(md, M, q, what=""):
+    """M against the kinetic energy's bilinear form (+ armature) on random velocity pairs and on every diagonal entry; any tree."""
     nv = md["nv"]
     rng = np.random.default_rng(0)
     # full bilinear form on random velocity pairs + every diagonal entry
     for _ in range(6):
         a, b = rng.normal(size=nv), rng.normal(size=nv)
         ref = _kinetic_bilinear(md, q, a, b) + a @ (np.asarray(md["dof_armature"]) * b)
-        assert abs(a @ M @ b - ref) < 1e-6 * max(1.0, abs(ref)), (example, a @ M @ b, ref)
+        assert abs(a @ M @ b - ref) < 1e-6 * max(1.0, abs(ref)), (what, a @ M @ b, ref)
     for i in range(nv):
         e = np.zeros(nv)
         e[i] = 1.0
         ref = _kinetic_bilinear(md, q, e, e) + md["dof_armature"][i]
-        assert abs(M[i, i] - ref) < 1e-6 * max(1.0, abs(ref)), (example, i)
+        assert abs(M[i, i] - ref) < 1e-6 * max(1.0, abs(ref)), (what, i)
+
+
+@pytest.mark.parametrize("example,_n", ROBOTS)
+def test_mass_matrix_is_the_hessian_of_the_kinetic_energy(example, _n):
+    env, md, model, task, cfg, q, qd = _case(example, 3)
+    o64 = O.Oracle(model, task, cfg, np.float64)
+    M = o64.forward_dump(q, np.zeros(md["nv"]))["qM"]
+    check_mass_matrix(md, M, q, example)
+
+
+def joint_coordinates(md):
+    """(dof indices, qpos addresses) of the slide / hinge joints -- the ordinary coordinates; the rest are free-joint dofs."""
+    dofs, qadr = [], []
+    for j in range(md["njnt"]):
+        if md["jnt_type"][j] != mjcf.JNT_FREE:
+            dofs.append(int(md["jnt_dofadr"][j]))
+            qadr.append(int(md["jnt_qposadr"][j]))
+    return np.array(dofs, int), np.array(qadr, int)
+
+
+def check_lagrange_bias(md, o64, q, qd, what=""):
+    """Every free base at rest: on the slide / hinge coordinates c = sum_k dM/dq_k qd_k qd - 1/2 d(qd^T M qd)/dq + dV/dq.  Any number
+    of free joints, anywhere in the dof order (none: a fixed-base model)."""
+    nv, nq = md["nv"], md["nq"]
+    dofs, qadr = joint_coordinates(md)
+    v = np.zeros(nv)
+    v[dofs] = np.asarray(qd)[dofs]
+    bias = o64.forward_dump(q, v)["qfrc_bias"]
+    g = np.asarray(md["gravity"], np.float64)
+
+    def Mh(qq):
+        return o64.forward_dump(qq, np.zeros(nv))["qM"][np.ix_(dofs, dofs)]
+
+    def V(qq):
+        k = mjcf.host_kinematics(md, qq)
+        return -sum(md["body_mass"][b] * g @ k["xipos"][b] for b in range(1, md["nbody"]))
+
+    h, nh = 1e-5, len(dofs)
+    th = v[dofs]
+    dM = np.zeros((nh, nh, nh))       # dM[k] = dM/dtheta_k
+    dV = np.zeros(nh)
+    for k in range(nh):
+        e = np.zeros(nq)
+        e[qadr[k]] = h
+        dM[k] = (Mh(q + e) - Mh(q - e)) / (2 * h)
+        dV[k] = (V(q + e) - V(q - e)) / (2 * h)
+    Mdot = np.einsum("kij,k->ij", dM, th)
+    c = Mdot @ th - 0.5 * np.einsum("kij,i,j->k", dM, th, th) + dV
+    assert np.allclose(bias[dofs], c, rtol=1e-5, atol=2e-5), (what, np.abs(bias[dofs] - c).max())
 
 
 @pytest.mark.parametrize("example,_n", ROBOTS)
@@ -90,31 +136,9 @@ def test_bias_forces_satisfy_lagranges_equations_on_the_hinges(example, _n):
     """Base at rest: on the hinge coordinates c = sum_k dM/dq_k qd_k qd - 1/2 d(qd^T M qd)/dq + dV/dq."""
     env, md, model, task, cfg, q, qd = _case(example, 5)
     o64 = O.Oracle(model, task, cfg, np.float64)
-    nv, nq = md["nv"], md["nq"]
-    v = np.array(qd)
-    v[:6] = 0.0
-    bias = o64.forward_dump(q, v)["qfrc_bias"]
-    g = np.asarray(md["gravity"], np.float64)
-
-    def Mh(qq):
-        return o64.forward_dump(qq, np.zeros(nv))["qM"][6:, 6:]
-
-    def V(qq):
-        k = mjcf.host_kinematics(md, qq)
-        return -sum(md["body_mass"][b] * g @ k["xipos"][b] for b in range(1, md["nbody"]))
-
-    h, nh = 1e-5, nv - 6
-    th = v[6:]
-    dM = np.zeros((nh, nh, nh))       # dM[k] = dM/dtheta_k
-    dV = np.zeros(nh)
-    for k in range(nh):
-        e = np.zeros(nq)
-        e[7 + k] = h
-        dM[k] = (Mh(q + e) - Mh(q - e)) / (2 * h)
-        dV[k] = (V(q + e) - V(q - e)) / (2 * h)
-    Mdot = np.einsum("kij,k->ij", dM, th)
-    c = Mdot @ th - 0.5 * np.einsum("kij,i,j->k", dM, th, th) + dV
-    assert np.allclose(bias[6:], c, rtol=1e-5, atol=2e-5), (example, np.abs(bias[6:] - c).max())
+    dofs, qadr = joint_coordinates(md)
+    assert np.array_equal(dofs, np.arange(6, md["nv"])) and np.array_equal(qadr, np.arange(7, md["nq"]))
+    check_lagrange_bias(md, o64, q, qd, example)
 
 
 @pytest.mark.parametrize("example,_n", ROBOTS)
@@ -182,19 +206,16 @@ def test_invweight0_and_meaninertia_follow_their_definitions(example, _n):
         assert np.allclose(md["body_invweight0"][b], ref, rtol=2e-5, atol=1e-9), (example, b, md["body_invweight0"][b], ref)
 
 
-@pytest.mark.parametrize("example,_n", ROBOTS[:2])
-def test_contact_jacobian_is_the_velocity_of_the_material_contact_point(example, _n):
-    env, md, model, task, cfg, _, _ = _case(example, 0)
-    q = np.array(env._init_q, np.float64)                     # home pose: every foot contact is active
+def check_floor_contact_jacobians(md, d, q, contacts, what=""):
+    """The pyramid rows of the contacts `contacts` (geom1 a plane with normal +z on the world body) against the finite-difference
+    velocity of the material contact point on body2.  Any tree."""
     nv = md["nv"]
-    o64 = O.Oracle(model, task, cfg, np.float64)
-    d = o64.forward_dump(q, np.zeros(nv))
-    assert np.all(d["con_dist"] < 0)
     k0 = mjcf.host_kinematics(md, q)
-    nl, nc = md["nlim"], md["ncon"]
+    nl = md["nlim"] + md.get("nfri", 0)
     rng = np.random.default_rng(1)
     eps = 1e-6
-    for c in range(nc):
+    for c in contacts:
+        assert int(md["con_body1"][c]) == 0, (what, c)
         b2 = int(md["con_body2"][c])
         p = d["con_pos"][c]
         ploc = k0["xmat"][b2].T @ (p - k0["xpos"][b2])
@@ -207,8 +228,18 @@ def test_contact_jacobian_is_the_velocity_of_the_material_contact_point(example,
             kp, km = mjcf.host_kinematics(md, _integrate(md, q, v, eps)), mjcf.host_kinematics(md, _integrate(md, q, v, -eps))
             vel = ((kp["xpos"][b2] + kp["xmat"][b2] @ ploc) - (km["xpos"][b2] + km["xmat"][b2] @ ploc)) / (2 * eps)
             comp = np.array([Jn @ v, Jt1 @ v, Jt2 @ v])
-            assert abs(comp[0] - vel[2]) < 1e-6 * max(1, abs(vel[2]))                  # normal = +z
-            assert abs(np.linalg.norm(comp) - np.linalg.norm(vel)) < 1e-6 * max(1, np.linalg.norm(vel))   # orthonormal frame
+            assert abs(comp[0] - vel[2]) < 1e-6 * max(1, abs(vel[2])), (what, c)                  # normal = +z
+            assert abs(np.linalg.norm(comp) - np.linalg.norm(vel)) < 1e-6 * max(1, np.linalg.norm(vel)), (what, c)   # orthonormal frame
+
+
+@pytest.mark.parametrize("example,_n", ROBOTS[:2])
+def test_contact_jacobian_is_the_velocity_of_the_material_contact_point(example, _n):
+    env, md, model, task, cfg, _, _ = _case(example, 0)
+    q = np.array(env._init_q, np.float64)                     # home pose: every foot contact is active
+    o64 = O.Oracle(model, task, cfg, np.float64)
+    d = o64.forward_dump(q, np.zeros(md["nv"]))
+    assert np.all(d["con_dist"] < 0)
+    check_floor_contact_jacobians(md, d, q, range(md["ncon"]), example)
 
 
 def _impedance_rows(md, q, v, d):

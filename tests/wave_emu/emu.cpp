@@ -14,6 +14,17 @@
 #include <vector>
 #include <xmmintrin.h>
 
+// -DDIAL_EMU_USER (a variant build, tests/emu_lib.py: user_variant): a task plugin's instantiation on the host -- DimsUser at the
+// dimensions DIAL_PLUGIN_NQ .. DIAL_PLUGIN_NFRI with the reward source DIAL_EMU_USER_REWARD, as csrc/plugin.hip instantiates it.
+// Path 0 takes it for a model of exactly those dimensions.  emu_set_user_params sets the reward's parameters: process-wide in this
+// library, copied into the staged constants by every call's Runner (each emu_* call builds one), so a later call sees a later set.
+#ifdef DIAL_EMU_USER
+#include DIAL_EMU_USER_REWARD
+using DimsEmuUser = DimsUser<DIAL_PLUGIN_NQ, DIAL_PLUGIN_NV, DIAL_PLUGIN_NU, DIAL_PLUGIN_NB, DIAL_PLUGIN_NJ, DIAL_PLUGIN_NG, DIAL_PLUGIN_NS,
+                             DIAL_PLUGIN_NC, DIAL_PLUGIN_NL, DIAL_PLUGIN_NFRI, false>;
+static float g_user_params[DIAL_USER_PARAMS];
+#endif
+
 namespace {
 
 template <class D>
@@ -22,6 +33,9 @@ struct Runner {
   int ws_words, con_cap = 0, ovf_words = 0;
   Runner(const dial_model* m, const dial_task* t, const dial_derived* dv) {
     fill_cmodel(&cm, m, t, dv);
+#ifdef DIAL_EMU_USER
+    if constexpr (D::user) for (int k = 0; k < DIAL_USER_PARAMS; k++) cm.user_params[k] = g_user_params[k];
+#endif
     Ws s;
     // DIAL_EMU_CON_CAP=k: the GPU rollout kernel's capped workspace (derived.h: ws_carve) + overflow area, on the host
     if (const char* e = std::getenv("DIAL_EMU_CON_CAP")) con_cap = D::gen ? std::atoi(e) : 0;
@@ -100,17 +114,34 @@ int run_env_reset(const dial_model* m, const dial_task* t, const dial_derived* d
   return w.races;
 }
 
+// (-DDIAL_EMU_SEGMENT_AS_PLANE: a measurement variant that runs such a model on the capacity dimensions all the same, i.e. reads those
+// slots with the plane formula as every pyramidal generic instantiation did before the narrow phases were opened to plugins)
+bool segment_contacts(const dial_model* m) {
+#ifdef DIAL_EMU_SEGMENT_AS_PLANE
+  return false;
+#endif
+  for (int c = 0; c < m->ncon; c++)
+    if (m->con_kind[c] == DIAL_CON_SPHERE_CAPSULE || m->con_kind[c] == DIAL_CON_CAPSULE_CAPSULE) return true;
+  return false;
+}
+#ifdef DIAL_EMU_USER
+#define DISPATCH_USER(path, m, CALL) if ((path) == 0 && dims_match<DimsEmuUser>(m)) return CALL(DimsEmuUser);
+#else
+#define DISPATCH_USER(path, m, CALL)
+#endif
 #define DISPATCH(path, m, CALL)                                        \
   if ((m)->cone == DIAL_CONE_ELLIPTIC) {                                \
     if (dims_match<DimsAllegro>(m) && ell_fits<DimsAllegro>(m, &dv)) return CALL(DimsAllegro); \
     return DIAL_ERR_UNSUPPORTED;   /* elliptic cones: dimension-specialised instantiations only */ \
   }                                                                    \
   if ((m)->eulerdamp) return DIAL_ERR_UNSUPPORTED;                     \
+  DISPATCH_USER(path, m, CALL)                                         \
   if ((path) == 0 && dims_match<DimsGo2>(m)) return CALL(DimsGo2);     \
   if ((path) == 0 && dims_match<DimsH1>(m)) return CALL(DimsH1);       \
   if ((path) == 0 && dims_match<DimsH1Loco>(m)) return CALL(DimsH1Loco); \
   if ((path) == 0 && dims_match<DimsGo2Crate>(m)) return CALL(DimsGo2Crate); \
   if ((path) == 0 && dims_match<DimsH1PushCrate>(m)) return CALL(DimsH1PushCrate); \
+  if (segment_contacts(m)) return DIAL_ERR_UNSUPPORTED;   /* as dial_create: pyramidal sphere- / capsule-capsule pairs need a plugin */ \
   return CALL(DimsMax);
 
 }  // namespace
@@ -171,6 +202,29 @@ int emu_sizes(const dial_model* m, int* cmodel_bytes, int* ws_words) {
   Runner<DimsMax> r(m, &t, &dv);
   *cmodel_bytes = (int)sizeof(r.cm);
   *ws_words = r.ws_words;
+  return 0;
+}
+#ifdef DIAL_EMU_USER
+int emu_set_user_params(const float* p, int n) {
+  for (int k = 0; k < DIAL_USER_PARAMS; k++) g_user_params[k] = k < n ? p[k] : 0.f;
+  return 0;
+}
+#endif
+// read-only view of the derived tables (csrc/derived.h: dial_build_derived): returns its code; levels[0] = nlevel, then lvl_start
+// [nlevel + 1] and lvl_body [nbody - 1]; masks = body_ancmask [nbody] then dof_ancmask [nv]; items = the packed H work list
+// (<= cap words), *nhitem its length
+int emu_derived(const dial_model* m, int* levels, unsigned* masks, int* nhitem, unsigned* items, int cap) {
+  dial_derived dv;
+  const int rc = dial_build_derived(m, &dv);
+  if (rc) return rc;
+  int k = 0;
+  levels[k++] = dv.nlevel;
+  for (int d = 0; d <= dv.nlevel; d++) levels[k++] = dv.lvl_start[d];
+  for (int b = 0; b < m->nbody - 1; b++) levels[k++] = dv.lvl_body[b];
+  for (int b = 0; b < m->nbody; b++) masks[b] = dv.body_ancmask[b];
+  for (int i = 0; i < m->nv; i++) masks[m->nbody + i] = dv.dof_ancmask[i];
+  *nhitem = dv.nhitem;
+  for (int e = 0; e < dv.nhitem && e < cap; e++) items[e] = dv.hitem[e];
   return 0;
 }
 // the kernel's box narrow phases (csrc/box_collide.h) on one pair: geoms as (pos[3], quat[4], size[3])
