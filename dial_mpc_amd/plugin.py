@@ -110,6 +110,41 @@ def check_topology(model) -> None:
         seen[dof] = a
 
 
+def _box_constants() -> tuple:
+    """(DIAL_BOX_POLY_WORDS, DIAL_BOX_PARK_DIST) of csrc/box_collide.h."""
+    text = open(os.path.join(_CSRC, "box_collide.h")).read()
+    words = re.search(r"#define\s+DIAL_BOX_POLY_WORDS\s+(\d+)", text)
+    park = re.search(r"#define\s+DIAL_BOX_PARK_DIST\s+([0-9.eE+-]+)f", text)
+    return int(words.group(1)), float(np.float32(park.group(1)))
+
+
+def check_box_contacts(model) -> None:
+    """Raise DialHipError for the two box conditions dial_create answers with DIAL_ERR_UNSUPPORTED: more box-box candidates than the
+    polygon scratch holds (their clipping polygons live in the dead velocity temporaries, 6 nv + 12 nbody words), and a box contact
+    whose margin reaches the distance beyond which the box narrow phases park a candidate."""
+    d = _model_dict(model)
+    ncon = int(d["ncon"])
+    if not ncon:
+        return
+    kind = np.asarray(d["con_kind"]).ravel()[:ncon]
+    words, park = _box_constants()
+    nbb = int((kind == _abi.MACROS["DIAL_CON_BOX_BOX"]).sum())
+    have = 6 * int(d["nv"]) + 12 * int(d["nbody"])
+    if nbb * words > have:
+        raise DialHipError(f"the model has {nbb} box-box candidate contacts (four per pair of box geoms); their clipping polygons need "
+                           f"{nbb * words} words of the kernels' polygon scratch ({words} each) and the model has {have} "
+                           "(6 nv + 12 nbody): exclude a box pair (<contact><exclude>, contype / conaffinity) -- dial_create refuses "
+                           "the model (too many box-box candidate contacts for the polygon scratch)")
+    margin = np.asarray(d["con_margin"]).ravel()[:ncon]
+    names = d.get("names", {}) if isinstance(d, dict) else {}
+    for c in range(ncon):
+        if kind[c] >= _abi.MACROS["DIAL_CON_PLANE_BOX"] and not np.float32(margin[c]) < np.float32(park):
+            g = [int(np.asarray(d[k]).ravel()[c]) for k in ("con_geom1", "con_geom2")]
+            who = [repr(names["geom"][k]) if names.get("geom") and k < len(names["geom"]) else str(k) for k in g]
+            raise DialHipError(f"the contact of geoms {who[0]} and {who[1]} has margin {float(margin[c]):g} m; box contacts need margin "
+                               f"< {park:g} m (DIAL_BOX_PARK_DIST: the box narrow phases park candidates that are further apart)")
+
+
 def check_model(model) -> None:
     """Raise DialHipError when a task plugin cannot serve `model` (csrc/plugin_ops.h: PluginOps::check)."""
     d = _model_dict(model)
@@ -120,6 +155,7 @@ def check_model(model) -> None:
                            "pyramidal kernels integrate it explicitly: add <option><flag eulerdamp=\"disable\"/></option> to the MJCF "
                            "(dial_create refuses eulerdamp on every pyramidal model)")
     check_topology(d)
+    check_box_contacts(d)
     n, cap = kbi_unique_rows(d), _kbi_rows_capacity()
     if n > cap:
         raise DialHipError(f"the model has {n} distinct (solref, solimp) sets; the impedance table of a plugin holds "

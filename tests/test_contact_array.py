@@ -7,7 +7,7 @@ import yaml
 
 import oracle as O
 from conftest import TOL, with_solver
-from dial_mpc_amd import mjcf
+from dial_mpc_amd import _abi, mjcf
 from dial_mpc_amd.core.dial_core import load_dial_and_env, make_cfg
 from dial_mpc_amd.utils.io_utils import get_example_path
 
@@ -92,26 +92,37 @@ def test_crate_climb_literal_positions_follow_the_layout():
 
 def test_extra_candidates_of_a_box_pair_are_parked():
     """A reference array may list a box pair more often than this compiler emits it (newer MJX: 8 box-box points): the extra
-    slots get the next con_sub and the geometry parks them (dist = 1, no rows) -- on the oracle and in the kernel logic."""
+    slots get the next con_sub and the geometry parks them (dist = 1, no rows) -- on the oracle and in the kernel logic.  Seven
+    candidates are what the model's polygon scratch holds (7 x 60 = 420 = 6 nv + 12 nbody words, exactly); with eight the last slice
+    would lie in live data, and the emulator refuses the model as dial_create does (the oracle, which has no such scratch, runs it)."""
     import emu_lib
     dc, _, env = _env("unitree_h1_push_crate")
     m = env.sys.model
     slots = mjcf.contact_slots(m, ids="mujoco")
     bb = [c for c in range(len(slots)) if int(m["con_kind"][c]) == 8]
     assert len(bb) == 4
-    layout = [list(p) for p in slots] + [list(slots[bb[0]])] * 4          # 8 candidates for the torso / crate pair
-    _, _, env8 = _env("unitree_h1_push_crate", contact_slots=layout)
-    m8 = env8.sys.model
-    assert int(m8["ncon"]) == 32 and int(m8["nefc"]) == int(m["nefc"]) + 16
-    assert [int(s) for s in np.asarray(m8["con_sub"])[-4:]] == [4, 5, 6, 7]
     cfg = make_cfg(dc)
     conv = lambda e: with_solver(e.make_model(), ls_rule=0, iterations=50, ls_iterations=50)  # noqa: E731
+    assert 6 * int(m["nv"]) + 12 * int(m["nbody"]) == 7 * 60
+    layout = [list(p) for p in slots] + [list(slots[bb[0]])] * 4          # 8 candidates for the torso / crate pair
+    _, _, env9 = _env("unitree_h1_push_crate", contact_slots=layout)
+    m9 = env9.sys.model
+    assert int(m9["ncon"]) == 32 and int(m9["nefc"]) == int(m["nefc"]) + 16
+    assert [int(s) for s in np.asarray(m9["con_sub"])[-4:]] == [4, 5, 6, 7]
+    s0, _, _ = O.Oracle(conv(env), env.make_task(), cfg, np.float32).env_reset(env._init_q, np.zeros(m["nv"]))
+    us = np.random.default_rng(1).uniform(-0.5, 0.5, (4, 9, int(m["nu"]))).astype(np.float32)
+    r9 = O.Oracle(conv(env9), env9.make_task(), cfg, np.float32).rollout(s0, us)
+    with pytest.raises(AssertionError, match=f"rc={_abi.MACROS['DIAL_ERR_UNSUPPORTED']}"):
+        emu_lib.Emu(conv(env9), env9.make_task(), cfg, path=1).rollout(s0, us)
+    _, _, env8 = _env("unitree_h1_push_crate", contact_slots=layout[:-1])   # 7 candidates: the scratch filled exactly
+    m8 = env8.sys.model
+    assert int(m8["ncon"]) == 31 and int(m8["nefc"]) == int(m["nefc"]) + 12
+    assert [int(s) for s in np.asarray(m8["con_sub"])[-3:]] == [4, 5, 6]
     o0 = O.Oracle(conv(env), env.make_task(), cfg, np.float32)
     o8 = O.Oracle(conv(env8), env8.make_task(), cfg, np.float32)
     emu8 = emu_lib.Emu(conv(env8), env8.make_task(), cfg, path=1)
-    s0, _, _ = o0.env_reset(env._init_q, np.zeros(m["nv"]))
-    us = np.random.default_rng(1).uniform(-0.5, 0.5, (4, 9, int(m["nu"]))).astype(np.float32)
-    r0, r8, re = o0.rollout(s0, us), o8.rollout(s0, us), emu8.rollout(s0, us)
-    for name, a, b, c in zip(("rewss", "q", "qd", "x"), r0, r8, re):
+    r0, r8, re = o0.rollout(s0, us), o8.rollout(s0, us), emu8.rollout(s0, us, check_races=True)
+    for name, a, b, c, d in zip(("rewss", "q", "qd", "x"), r0, r8, re, r9):
         assert np.allclose(a, b, rtol=TOL[name]["rtol"], atol=TOL[name]["atol"]), name
+        assert np.allclose(a, d, rtol=TOL[name]["rtol"], atol=TOL[name]["atol"]), name      # (the oracle with all eight)
         assert np.allclose(a, c, rtol=TOL[name]["rtol"], atol=TOL[name]["atol"]), name

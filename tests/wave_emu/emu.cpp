@@ -124,6 +124,16 @@ bool segment_contacts(const dial_model* m) {
     if (m->con_kind[c] == DIAL_CON_SPHERE_CAPSULE || m->con_kind[c] == DIAL_CON_CAPSULE_CAPSULE) return true;
   return false;
 }
+// as dial_create: the box-box candidates' clipping polygons are slices of the dead velocity temporaries (6 nv + 12 nbody words of the
+// MODEL's dimensions, whatever the instantiation's), and a box contact's margin stays below the parking distance
+bool box_contacts_refused(const dial_model* m) {
+  int nbb = 0;
+  for (int c = 0; c < m->ncon; c++) nbb += m->con_kind[c] == DIAL_CON_BOX_BOX ? 1 : 0;
+  if (nbb * DIAL_BOX_POLY_WORDS > 6 * m->nv + 12 * m->nbody) return true;
+  for (int c = 0; c < m->ncon; c++)
+    if (m->con_kind[c] >= DIAL_CON_PLANE_BOX && !(m->con_margin[c] < DIAL_BOX_PARK_DIST)) return true;
+  return false;
+}
 #ifdef DIAL_EMU_USER
 #define DISPATCH_USER(path, m, CALL) if ((path) == 0 && dims_match<DimsEmuUser>(m)) return CALL(DimsEmuUser);
 #else
@@ -135,6 +145,7 @@ bool segment_contacts(const dial_model* m) {
     return DIAL_ERR_UNSUPPORTED;   /* elliptic cones: dimension-specialised instantiations only */ \
   }                                                                    \
   if ((m)->eulerdamp) return DIAL_ERR_UNSUPPORTED;                     \
+  if (box_contacts_refused(m)) return DIAL_ERR_UNSUPPORTED;            \
   DISPATCH_USER(path, m, CALL)                                         \
   if ((path) == 0 && dims_match<DimsGo2>(m)) return CALL(DimsGo2);     \
   if ((path) == 0 && dims_match<DimsH1>(m)) return CALL(DimsH1);       \
